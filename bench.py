@@ -7,7 +7,14 @@ E=95,424 active edges, 2 BA iterations), inputs resident in HBM.
 Multi-GPU: one independent sequence per rank (seed = rank), no collective in
 the timed region (weak scaling); poses/points are gathered over RCCL after.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes what the last timed update() left for its
+caller (dump_arrays) as DIR/<name>.npy.  --full adds everything measured
+around the headline figure: altcorr events inside the timed loop, the host
+calibration, the per-phase breakdown and roofline objects, the CPU baseline
+and the end-to-end frames/s.
 """
 import argparse
 import hashlib
@@ -83,15 +90,22 @@ def parse():
                     help="C3 (the metric's workload, default) or C2 (512-KF buffer, M=96, 8 BA iterations)")
     ap.add_argument("--buffer", type=int, default=None)
     ap.add_argument("--iterations", type=int, default=None)
-    ap.add_argument("--e2e-frames", type=int, default=32, help="end-to-end frames timed after the bench (0: skip)")
+    ap.add_argument("--e2e-frames", type=int, default=32, help="--full: end-to-end frames timed after the bench (0: skip)")
     ap.add_argument("--exact-corr", action="store_true", help="the bit-exact fp16-chain altcorr instead of the MFMA one")
     ap.add_argument("--graph", action="store_true",
                     help="replay update() from a HIP graph (captured in the warmup) instead of launching it eagerly")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-edges", type=int, default=1500)
     ap.add_argument("--counters-json", default=COUNTERS_JSON,
                     help="rocprofv3 counter record of the same kernel versions (scripts/counters_json.py)")
     ap.add_argument("--no-affinity", action="store_true", help="do not pin this rank's host threads")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what surrounds the headline figure: altcorr events in the timed loop, host "
+                         "calibration, per-phase breakdown, roofline objects, CPU baseline (--no-cpu-baseline, "
+                         "--cpu-sample-edges) and end-to-end frames/s (--e2e-frames)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the last timed update() produced (rank 0's "
+                         "sequence) as DIR/<name>.npy in float32; see dump_arrays")
     return ap.parse_args()
 
 
@@ -166,6 +180,48 @@ def gather_to_rank0(tensors, rank, world):
         dist.gather(t, bufs, dst=0)
         out.append(bufs)
     return out if rank == 0 else None
+
+
+DUMP_ARRAY_BYTES = 10 << 20   # per array; six arrays stay under 64 MB in all
+
+
+def sample_rows(rows, itemsize_row, seed, max_bytes=DUMP_ARRAY_BYTES):
+    """all row indices if they fit max_bytes, else a seeded, sorted sample of
+    them (the same rows on every run and every build); None means all rows"""
+    keep = max_bytes // itemsize_row
+    if rows <= keep:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(rows, size=keep, replace=False))
+
+
+def dump_arrays(slam):
+    """What update() leaves for its caller (it returns nothing: the tracker
+    reads its state), as float32 host arrays, rows along the first axis:
+      poses   [n, 7]       keyframe poses after BA
+      patches [n M, 27]    patches of the n keyframes (BA updates their inverse depths)
+      points  [m, 3]       point cloud of the m stored patches
+      net     [E, 384]     the update operator's edge state
+      target  [E, 2], weight [E, 2]   the BA targets and confidences of the edges
+    An array above DUMP_ARRAY_BYTES keeps a fixed seeded sample of its rows
+    (sample_rows, seed = position in this list)."""
+    n, m = slam.n, slam.pg.m
+    full = (("poses", slam.pg.poses_[:n]), ("patches", slam.pg.patches_[:n].reshape(n * slam.M, -1)),
+            ("points", slam.pg.points_[:m]), ("net", slam.pg.net[0]), ("target", slam.pg.target[0]),
+            ("weight", slam.pg.weight[0]))
+    out = {}
+    for seed, (name, t) in enumerate(full):
+        t = t.reshape(t.shape[0], -1)
+        idx = sample_rows(t.shape[0], 4 * t.shape[1], seed)
+        if idx is not None:
+            t = t[torch.from_numpy(idx).to(t.device)]
+        out[name] = t.float().cpu().numpy()
+    return out
+
+
+def write_arrays(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 class CorrProbe:
@@ -586,15 +642,18 @@ def main():
                                 device=f"cuda:{local}", EXACT_CORR=args.exact_corr, **cfgd["overrides"])
     E = slam.pg.ii.numel()
     probe = CorrProbe()
-    probe.wrap(slam)
+    if args.full:
+        probe.wrap(slam)
 
     # update() makes no host read (BA's status is checked after the loop,
     # slam.check_ba).  --graph captures it once into a HIP graph during the
     # warmup and replays it (the patch graph does not change between steps);
     # within box spread of eager on one GPU (profiles/r4/bench_c3_graph_r4.json),
-    # so eager is the default and the corr events below time every launch live
-    with torch.no_grad():
-        host = host_cost(slam, args.cores)
+    # so eager is the default and (--full) the corr events below time every launch live
+    host = None
+    if args.full or world > 1:
+        with torch.no_grad():
+            host = host_cost(slam, args.cores)
     # each rank launches from its own pinned cores: replay update() from a HIP
     # graph (one launch per step) when a rank's launching thread is busy for
     # more than half of its step -- host jitter could then starve its GPU
@@ -614,19 +673,24 @@ def main():
         barrier(world)
         elapsed = time.perf_counter() - t0
         c1, p1 = time.thread_time(), time.process_time()
-        # every timed launch (eager); with --graph the captured launches are
-        # not evented (ROCm torch has no event-record nodes), so the probe
-        # falls back to a short eager pass after the loop
-        corr_ms, order_ms = probe.mean_ms("corr"), probe.mean_ms("order")
-        if graph:
-            for _ in range(3):
-                slam.update()
-            torch.cuda.synchronize()
-            corr_ms, order_ms = probe.mean_ms("corr"), probe.mean_ms("order")
         slam.check_ba()
-        breakdown = phase_breakdown(slam)
-        if not slam.cfg.EXACT_CORR:
-            breakdown["ingest_gmap_pack"] = gmap_pack_ms(slam)
+        # the state as the last timed step left it, before anything below runs more updates
+        if args.dump_outputs and rank == 0:
+            write_arrays(args.dump_outputs, dump_arrays(slam))
+        if args.full:
+            # every timed launch (eager); with --graph the captured launches are
+            # not evented (ROCm torch has no event-record nodes), so the probe
+            # falls back to a short eager pass after the loop
+            corr_ms, order_ms = probe.mean_ms("corr"), probe.mean_ms("order")
+            if graph:
+                for _ in range(3):
+                    slam.update()
+                torch.cuda.synchronize()
+                corr_ms, order_ms = probe.mean_ms("corr"), probe.mean_ms("order")
+                slam.check_ba()
+            breakdown = phase_breakdown(slam)
+            if not slam.cfg.EXACT_CORR:
+                breakdown["ingest_gmap_pack"] = gmap_pack_ms(slam)
 
     gather_ms = None
     if world > 1:
@@ -640,8 +704,6 @@ def main():
 
     if rank == 0:
         value = world * args.steps / elapsed
-        counters = load_counters(args.counters_json, E)
-        roof, roof_upd = roofline_lines(slam, corr_ms, order_ms, breakdown, counters, args.counters_json)
         metric = METRIC if args.buffer == 2048 else METRIC.replace("2048-KF buffer", f"{args.buffer}-KF buffer")
         line = {
             "metric": metric, "value": round(value, 3), "unit": "keyframes/s", "n_gpus": world,
@@ -654,20 +716,28 @@ def main():
                        "patches_per_frame": slam.M, "buffer": args.buffer, "n_keyframes": slam.n, "edges": E,
                        "ba_iterations": slam.cfg.BA_ITERATIONS, "image": "512x384",
                        "parallelism": f"replicas{world}"},
-            "roofline": roof,
-            "roofline_update_op": roof_upd,
-            "breakdown_ms": breakdown,
-            "fastba_us_per_iteration": round(breakdown["fastba"] * 1e3 / slam.cfg.BA_ITERATIONS, 2),
             "host_cores": {"rank0": _core_str(args.cores), "cpu_model": _cpu_model()},
             "host_ms_per_step": round((c1 - c0) / args.steps * 1e3, 4),
             "host_process_ms_per_step": round((p1 - p0) / args.steps * 1e3, 4),
-            "host_calibration": host,
         }
+        if host is not None:
+            line["host_calibration"] = host
+        if args.dump_outputs:
+            line["outputs"] = args.dump_outputs
+        if args.full:
+            counters = load_counters(args.counters_json, E)
+            roof, roof_upd = roofline_lines(slam, corr_ms, order_ms, breakdown, counters, args.counters_json)
+            line.update({
+                "roofline": roof,
+                "roofline_update_op": roof_upd,
+                "breakdown_ms": breakdown,
+                "fastba_us_per_iteration": round(breakdown["fastba"] * 1e3 / slam.cfg.BA_ITERATIONS, 2),
+            })
         if gather_ms is not None:
             line["gather_ms"] = gather_ms
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(slam, args.cpu_sample_edges, slam.cfg.BA_ITERATIONS)
-        if world == 1 and args.e2e_frames > 0:
+        if args.full and world == 1 and args.e2e_frames > 0:
             del slam
             torch.cuda.empty_cache()
             e2e = end_to_end(cfgd, args.buffer, args.iterations, args.e2e_frames, device=f"cuda:{local}")

@@ -44,6 +44,34 @@ def test_counter_record_only_for_current_sources(tmp_path):
     assert bench.load_counters(str(tmp_path / "missing.json"), 100) is None
 
 
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: an array within the per-array bound is written whole;
+    a larger one keeps the same sorted, distinct rows on every call, as many
+    as fit the bound; six arrays at the bound stay under 64 MB"""
+    import numpy as np
+
+    import bench
+    assert bench.sample_rows(100, 4 * 7, seed=0) is None
+    assert bench.sample_rows(1000, 40, seed=0, max_bytes=40000) is None
+    a = bench.sample_rows(1001, 40, seed=3, max_bytes=40000)
+    b = bench.sample_rows(1001, 40, seed=3, max_bytes=40000)
+    assert a.shape == (1000,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 1001
+    assert not np.array_equal(a, bench.sample_rows(1001, 40, seed=4, max_bytes=40000))
+    assert 6 * bench.DUMP_ARRAY_BYTES <= 64 * 10**6
+
+
+def test_write_arrays_float32_npy(tmp_path):
+    import numpy as np
+
+    import bench
+    arrays = {"poses": np.arange(14, dtype=np.float64).reshape(2, 7), "net": np.ones((3, 4), np.float16)[:, ::2]}
+    bench.write_arrays(str(tmp_path / "sub" / "dir"), arrays)
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "sub" / "dir" / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape == a.shape and np.array_equal(got, a.astype(np.float32))
+
+
 def test_torch_scatter_shim_refuses_host_tensors():
     import torch_scatter
     assert os.path.dirname(torch_scatter.__file__) == PKG

@@ -71,7 +71,7 @@ def test_bench_main_two_ranks_under_torchrun(tmp_path):
     env = dict(os.environ, DPVO_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}", os.path.join(repo, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--buffer", "72", "--no-cpu-baseline",
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--buffer", "72", "--full", "--no-cpu-baseline",
            "--e2e-frames", "0"]
     r = subprocess.run(cmd, env=env, cwd=repo, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -80,4 +80,5 @@ def test_bench_main_two_ranks_under_torchrun(tmp_path):
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["value"] > 0
     assert line["gather_ms"] >= 0
+    assert line["breakdown_ms"]["update_op"] > 0 and line["host_calibration"]["gpu_ms"] > 0   # --full
     assert line["value"] == pytest.approx(2 * 3 / (line["ms_per_step"] * 3 / 1e3), rel=1e-3)

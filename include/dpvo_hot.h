@@ -201,6 +201,27 @@ int dpvo_ba_forward_csr(float* poses, float* patches, int64_t num_patches, int P
                         int flags, const int* csr_offs, const int* csr_perm, const int64_t* csr_groups,
                         void* workspace, size_t workspace_bytes, int* status, void* stream);
 
+/* dpvo_ba_forward_csr with the depth prior of the reference's Python BA
+ * (dpvo/ba.py:151-159; its CUDA fastba has no such term).  patches_est
+ * [num_patches][3][P][P] (device, the layout of patches; only channel 2 at
+ * the centre pixel is read) holds one prior inverse depth per patch.  A patch
+ * k with a valid prior, 0 < est_k < +inf, adds
+ *     C_k += prior_mu,   u_k -= prior_mu * (d_k - est_k)
+ * to its normal equations before Q_k = 1 / (C_k + lmbda) is formed, in every
+ * iteration and on all three solver paths; est_k <= 0, +inf or NaN means "no
+ * prior".  (The reference tests est > 0 only, which lets 1 / median(depth) =
+ * inf through and turns the depth into NaN: the finite test is a deliberate
+ * guard.)  patches_est == NULL or prior_mu == 0 is exactly
+ * dpvo_ba_forward_csr; a negative or non-finite prior_mu is an error.  The
+ * workspace is that of dpvo_ba_workspace_bytes_ex. */
+int dpvo_ba_forward_prior(float* poses, float* patches, int64_t num_patches, int P, const float* intrinsics,
+                          const float* target, const float* weight, const float* lmbda,
+                          const float* patches_est, float prior_mu,
+                          const int64_t* ii, const int64_t* jj, const int64_t* kk, int64_t num_edges,
+                          int t0, int t1, int iterations, int flags,
+                          const int* csr_offs, const int* csr_perm, const int64_t* csr_groups,
+                          void* workspace, size_t workspace_bytes, int* status, void* stream);
+
 /* cuda_ba.reproject (ba_cuda.cu:368-418,543-575): coords [E][2][P][P]. */
 int dpvo_reproject(const float* poses, const float* patches, int P, const float* intrinsics, const int64_t* ii,
                    const int64_t* jj, const int64_t* kk, int64_t num_edges, float* coords, void* stream);

@@ -54,6 +54,8 @@ _SIGNATURES = {
                                  _vp, _sz, _vp, _vp]),
     "dpvo_ba_forward_csr": (_ip, [_vp, _vp, _i64, _ip, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _ip, _ip, _ip, _ip,
                                   _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "dpvo_ba_forward_prior": (_ip, [_vp, _vp, _i64, _ip, _vp, _vp, _vp, _vp, _vp, _fp, _vp, _vp, _vp, _i64, _ip, _ip,
+                                    _ip, _ip, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "dpvo_reproject": (_ip, [_vp, _vp, _ip, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "dpvo_solve_system_assemble": (_ip, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _fp, _fp, _vp, _vp, _vp, _vp]),
     "dpvo_neighbors_workspace_bytes": (_sz, [_i64]),

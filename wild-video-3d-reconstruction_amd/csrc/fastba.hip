@@ -22,6 +22,7 @@
 // The unique-id inverse (the reference's torch::_unique, ba_cuda.cu:435) is
 // recomputed per edge from the bitmap instead of being stored.
 #include <algorithm>
+#include <cfloat>
 #include <stdlib.h>
 
 #include <hipcub/hipcub.hpp>
@@ -226,9 +227,33 @@ struct BaParams {
     double* St;      // band tiles of the reduced camera system, lower triangle (fp64)
     double* ys;      // [T * 64] right-hand side, then the solution dX (fp64)
     int T, bt;       // 64-wide tiles per side, tile bandwidth
+    // depth prior (dpvo_ba_forward_prior): nullptr = the plain call
+    const float* est; // [num_patches][3][P][P], channel 2 at the centre pixel
+    float mu;
 };
 
 __device__ __forceinline__ bool failed(const BaParams& p) { return *(volatile int*)p.status != 0; }
+
+// Depth prior of the reference's Python BA (dpvo/ba.py:151-159): a patch with
+// a prior inverse depth est adds mu to C and -mu (d - est) to u before
+// Q = 1 / (C + lmbda) is formed.  Valid is 0 < est < +inf: the reference's
+// est > 0 alone lets 1 / median(depth) = inf through, and the depth turns NaN.
+__device__ __forceinline__ bool prior_valid(float est) { return est > 0.f && est < __builtin_inff(); }
+
+// atomic dense path: the prior enters C / u once, as the value the
+// accumulators of unique patch k start an iteration from (0 without a prior)
+__device__ __forceinline__ void prior_seed(const BaParams& p, int64_t k, float& C0, float& u0)
+{
+    C0 = 0.f;
+    u0 = 0.f;
+    if (p.est == nullptr) return;
+    const int64_t PP = (int64_t)p.P * p.P, at = ((int64_t)p.kx[k] * 3 + 2) * PP + (p.P / 2) * p.P + p.P / 2;
+    const float est = p.est[at];
+    if (prior_valid(est)) {
+        C0 = p.mu;
+        u0 = -p.mu * (p.patches[at] - est);
+    }
+}
 
 // ---------------------------------------------------------------------------
 // unique(kk): bitmap + popcount prefix
@@ -331,12 +356,18 @@ __global__ __launch_bounds__(256) void ba_zero_kernel(BaParams p)
 {
     const int Mu = p.hdr[HDR_MU];
     const int64_t nE = (int64_t)Mu * p.n6, nB = (int64_t)p.n6 * p.n6;
-    const int64_t total = nE + 2 * (int64_t)Mu + nB + p.n6 + nB + p.n6;
+    const int64_t total = nE + (int64_t)Mu + nB + p.n6 + nB + p.n6;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         int64_t j = i;
         if (j < nE) { p.Em[j] = 0.f; continue; } j -= nE;
-        if (j < Mu) { p.C[j] = 0.f; continue; } j -= Mu;
-        if (j < Mu) { p.u[j] = 0.f; continue; } j -= Mu;
+        if (j < Mu) {   // C and u of patch j together (the depth prior's seed, else 0)
+            float C0, u0;
+            prior_seed(p, j, C0, u0);
+            p.C[j] = C0;
+            p.u[j] = u0;
+            continue;
+        }
+        j -= Mu;
         if (j < nB) { p.B[j] = 0.f; continue; } j -= nB;
         if (j < p.n6) { p.v[j] = 0.f; continue; } j -= p.n6;
         if (j < nB) { p.S[j] = 0.f; continue; } j -= nB;
@@ -941,8 +972,10 @@ __global__ __launch_bounds__(256) void ba_patch_kernel(BaParams p, int structure
         d = fmaxf(d, 1e-4f);
         for (int64_t q = 0; q < PP; q++) pd[q] = d;
         if (reset) {
-            p.C[k] = 0.f;
-            p.u[k] = 0.f;
+            float C0, u0;
+            prior_seed(p, k, C0, u0);   // (reads the depth stored above)
+            p.C[k] = C0;
+            p.u[k] = u0;
             for (int a = 0; a < n6; a++) Erow[a] = 0.f;
         }
     }
@@ -1041,6 +1074,14 @@ __global__ __launch_bounds__(256) void bs_schur_kernel(BaParams p)
             C += d.x;
             u += d.y;
             uniform = uniform && p.ii[e] == hpose;
+        }
+        if (p.est != nullptr && live) {   // depth prior, before Q, Qk and uk are formed
+            const int64_t PP = (int64_t)p.P * p.P, at = ((int64_t)p.kx[k] * 3 + 2) * PP + (p.P / 2) * p.P + p.P / 2;
+            const float est = p.est[at];
+            if (prior_valid(est)) {
+                C += p.mu;
+                u -= p.mu * (p.patches[at] - est);
+            }
         }
         const float Q = 1.0f / (C + lm);
         if (live) {
@@ -1639,6 +1680,9 @@ struct BdParams {
     bd_i4v* grec;
     int* status;
     float *Em, *Cg, *ug, *Hpart, *H, *Hd, *dX;
+    // depth prior (dpvo_ba_forward_prior): nullptr = the plain call
+    const float* est;      // [num_patches][3][P][P], channel 2 at the centre pixel
+    float mu;
 };
 
 // row-major upper triangle of the n6 x n6 system, a <= b
@@ -1969,6 +2013,15 @@ __global__ __launch_bounds__(64 * BD_WAVES) void bd_patch_kernel(BdParams p)
         }
         if (!HESS) continue;   // (leaves the do-while: the next iteration)
         const float px = p.patches[(k * 3 + 0) * PP + centre], py = p.patches[(k * 3 + 1) * PP + centre];
+        // depth prior: one centre-pixel load per patch, in flight with px / py;
+        // p.est is a kernel argument, so the test is wave-uniform and the plain
+        // call (nullptr) issues nothing
+        float est = 0.f;
+        if (p.est != nullptr) {
+            float e0 = 0.f;
+            if (lane == 0) e0 = p.est[(k * 3 + 2) * PP + centre];
+            est = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(e0)));
+        }
 
         if (pose_terms) {
             if (lane < n6) ev[lane] = 0.f;
@@ -2051,6 +2104,13 @@ __global__ __launch_bounds__(64 * BD_WAVES) void bd_patch_kernel(BdParams p)
             }
         }
         BD_STAMP(ti2)
+        // dk is this iteration's depth (post-APPLY).  Added after the edge sums,
+        // in this fixed place: the path stays bitwise repeatable.  The stored
+        // Cg / ug carry the term, so the next launch's APPLY needs nothing new.
+        if (prior_valid(est)) {
+            Ck += p.mu;
+            uk -= p.mu * (dk - est);
+        }
         if (!pose_terms) {
             if (lane == 0) { p.Cg[g] = Ck; p.ug[g] = uk; }
             continue;
@@ -2586,17 +2646,23 @@ extern "C" int dpvo_diag_bd_stamps(void* host, size_t bytes)
 }
 #endif
 
-extern "C" int dpvo_ba_forward_csr(float* poses, float* patches, int64_t num_patches, int P, const float* intrinsics,
-                                   const float* target, const float* weight, const float* lmbda, const int64_t* ii,
-                                   const int64_t* jj, const int64_t* kk, int64_t num_edges, int t0, int t1,
-                                   int iterations, int flags, const int* csr_offs, const int* csr_perm,
-                                   const int64_t* csr_groups, void* workspace, size_t workspace_bytes, int* status,
-                                   void* stream)
+// The one implementation behind the four dpvo_ba_forward* exports: the
+// deterministic per-patch path, else the sparse band path, else the atomic
+// dense path.  patches_est == NULL or prior_mu == 0: no depth prior.
+extern "C" int dpvo_ba_forward_prior(float* poses, float* patches, int64_t num_patches, int P,
+                                     const float* intrinsics, const float* target, const float* weight,
+                                     const float* lmbda, const float* patches_est, float prior_mu, const int64_t* ii,
+                                     const int64_t* jj, const int64_t* kk, int64_t num_edges, int t0, int t1,
+                                     int iterations, int flags, const int* csr_offs, const int* csr_perm,
+                                     const int64_t* csr_groups, void* workspace, size_t workspace_bytes, int* status,
+                                     void* stream)
 {
     const int N = t1 - t0;
     DPVO_CHECK_ARG(N >= 0, "t1 must be >= t0");
     DPVO_CHECK_ARG(N <= BS_NMAX, "more than 32767 optimised poses");
     DPVO_CHECK_ARG(P >= 1 && num_patches >= 0 && iterations >= 0, "bad sizes");
+    DPVO_CHECK_ARG(prior_mu >= 0.f && prior_mu <= FLT_MAX, "prior_mu must be finite and >= 0");
+    const float* est = prior_mu > 0.f ? patches_est : nullptr;
     hipStream_t s = as_stream(stream);
     char* ws = (char*)workspace;
     if (ba_det(N, flags)) {
@@ -2608,6 +2674,7 @@ extern "C" int dpvo_ba_forward_csr(float* poses, float* patches, int64_t num_pat
         p.poses = poses; p.patches = patches; p.intrinsics = intrinsics; p.target = target; p.weight = weight;
         p.lmbda = lmbda; p.ii = ii; p.jj = jj; p.kk = kk; p.num_patches = num_patches; p.mu_max = L.mu_max;
         p.P = P; p.t0 = t0; p.N = N; p.n6 = L.n6; p.nup = L.nup; p.ent = L.ent;
+        p.est = est; p.mu = prior_mu;
         p.status = status ? status : (int*)(ws + L.hdr) + HDR_STATUS;
         // KEEP_STATUS: the caller's word may already hold a failure (the
         // tracker's window-key check); every bd_* kernel returns on entry when
@@ -2616,31 +2683,11 @@ extern "C" int dpvo_ba_forward_csr(float* poses, float* patches, int64_t num_pat
         if (num_edges == 0 || iterations == 0) return 0;
         return ba_forward_det(p, ws, L, num_edges, csr_offs, csr_perm, csr_groups, iterations, s);
     }
-    return dpvo_ba_forward_ex(poses, patches, num_patches, P, intrinsics, target, weight, lmbda, ii, jj, kk,
-                              num_edges, t0, t1, iterations, flags | DPVO_BA_ATOMIC, workspace, workspace_bytes, status,
-                              stream);
-}
-
-extern "C" int dpvo_ba_forward_ex(float* poses, float* patches, int64_t num_patches, int P, const float* intrinsics,
-                                  const float* target, const float* weight, const float* lmbda, const int64_t* ii,
-                                  const int64_t* jj, const int64_t* kk, int64_t num_edges, int t0, int t1,
-                                  int iterations, int flags, void* workspace, size_t workspace_bytes, int* status,
-                                  void* stream)
-{
-    const int N = t1 - t0;
-    DPVO_CHECK_ARG(N >= 0, "t1 must be >= t0");
-    DPVO_CHECK_ARG(N <= BS_NMAX, "more than 32767 optimised poses");
-    DPVO_CHECK_ARG(P >= 1 && num_patches >= 0 && iterations >= 0, "bad sizes");
-    if (ba_det(N, flags))
-        return dpvo_ba_forward_csr(poses, patches, num_patches, P, intrinsics, target, weight, lmbda, ii, jj, kk,
-                                   num_edges, t0, t1, iterations, flags, nullptr, nullptr, nullptr, workspace,
-                                   workspace_bytes, status, stream);
-    hipStream_t s = as_stream(stream);
-    char* ws = (char*)workspace;
     BaParams p{};
     p.poses = poses; p.patches = patches; p.intrinsics = intrinsics; p.target = target; p.weight = weight;
     p.lmbda = lmbda; p.ii = ii; p.jj = jj; p.kk = kk; p.E = num_edges; p.num_patches = num_patches;
     p.P = P; p.t0 = t0; p.N = N; p.n6 = 6 * N;
+    p.est = est; p.mu = prior_mu;
     if (ba_sparse(N, flags)) {
         const BsLayout L = bs_layout(num_edges, num_patches, N);
         DPVO_CHECK_ARG(workspace && workspace_bytes >= L.total, "workspace too small");
@@ -2703,6 +2750,29 @@ extern "C" int dpvo_ba_forward_ex(float* poses, float* patches, int64_t num_patc
         DPVO_CHECK_LAUNCH();
     }
     return 0;
+}
+
+extern "C" int dpvo_ba_forward_csr(float* poses, float* patches, int64_t num_patches, int P, const float* intrinsics,
+                                   const float* target, const float* weight, const float* lmbda, const int64_t* ii,
+                                   const int64_t* jj, const int64_t* kk, int64_t num_edges, int t0, int t1,
+                                   int iterations, int flags, const int* csr_offs, const int* csr_perm,
+                                   const int64_t* csr_groups, void* workspace, size_t workspace_bytes, int* status,
+                                   void* stream)
+{
+    return dpvo_ba_forward_prior(poses, patches, num_patches, P, intrinsics, target, weight, lmbda, nullptr, 0.f, ii,
+                                 jj, kk, num_edges, t0, t1, iterations, flags, csr_offs, csr_perm, csr_groups,
+                                 workspace, workspace_bytes, status, stream);
+}
+
+extern "C" int dpvo_ba_forward_ex(float* poses, float* patches, int64_t num_patches, int P, const float* intrinsics,
+                                  const float* target, const float* weight, const float* lmbda, const int64_t* ii,
+                                  const int64_t* jj, const int64_t* kk, int64_t num_edges, int t0, int t1,
+                                  int iterations, int flags, void* workspace, size_t workspace_bytes, int* status,
+                                  void* stream)
+{
+    return dpvo_ba_forward_prior(poses, patches, num_patches, P, intrinsics, target, weight, lmbda, nullptr, 0.f, ii,
+                                 jj, kk, num_edges, t0, t1, iterations, flags, nullptr, nullptr, nullptr, workspace,
+                                 workspace_bytes, status, stream);
 }
 
 extern "C" int dpvo_ba_forward(float* poses, float* patches, int64_t num_patches, int P, const float* intrinsics,

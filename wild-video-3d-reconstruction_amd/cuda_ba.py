@@ -23,7 +23,16 @@ Windows of more than 64 optimised poses (the global BA of dpvo.py:436-505)
 take the sparse path automatically: per-edge Schur entries and a tiled band
 Cholesky instead of the dense E / S (see include/dpvo_hot.h).  ``SPARSE =
 True`` forces it for any window (used by the parity tests).
+
+``patches_est=`` / ``prior_mu=`` (not in the reference's extension) add the
+depth prior of the reference's Python BA (dpvo/ba.py:151-159) on all three
+paths: a patch whose prior inverse depth (channel 2, centre pixel of
+``patches_est``, laid out like ``patches``) is positive and finite is pulled
+towards it with weight ``prior_mu``.  None (or ``prior_mu = 0``) is the plain
+call, bit for bit.
 """
+import math
+
 import torch
 
 import _dpvo_hot as H
@@ -49,7 +58,7 @@ def raise_for_status(s):
 
 
 def forward(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, iterations, csr=None,
-            status=None, keep_status=False):
+            status=None, keep_status=False, patches_est=None, prior_mu=2.0):
     """ba.cpp:31-43 -> ba_cuda.cu:422-540.  Updates poses and patches in place; returns [].
     csr (optional, not in the reference): (offs int32 [E+1], perm int32 [E],
     groups int64 [1]) of update_ops.group_by(kk) for these edges.
@@ -58,17 +67,30 @@ def forward(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t
     synchronisation; the caller checks it later (raise_for_status).
     keep_status (with status=): the word is not cleared first; if it already
     holds a failure (DPVO.update's window-key check) the call leaves poses and
-    patches untouched (deterministic sliding-window path, DPVO_BA_KEEP_STATUS)."""
+    patches untouched (deterministic sliding-window path, DPVO_BA_KEEP_STATUS).
+    patches_est, prior_mu (optional, not in the reference's extension): the
+    depth prior of dpvo/ba.py:151-159 -- one prior inverse depth per patch, in
+    the layout of patches (channel 2 at the centre pixel is read; <= 0, inf or
+    NaN: no prior for that patch), and its weight mu."""
     global last_status
+    if patches_est is not None and not patches_est.is_cuda:
+        raise RuntimeError("patches_est must be a GPU (HIP) tensor; this library has no CPU backend")
     H.on_gpu(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk)
     for name, t in (("poses", poses), ("patches", patches), ("intrinsics", intrinsics), ("target", target),
-                    ("weight", weight)):
+                    ("weight", weight), ("patches_est", patches_est)):
+        if t is None:
+            continue
         if t.dtype != torch.float32:
             raise RuntimeError(f"{name} must be float32")
         if not t.is_contiguous():
             raise RuntimeError(f"{name} must be contiguous (the reference views it, ba_cuda.cu:446-451)")
     P = patches.shape[3] if patches.dim() == 5 else patches.shape[-1]
     num_patches = patches.numel() // (3 * P * P)
+    if patches_est is not None and (patches_est.numel() != patches.numel() or patches_est.device != patches.device):
+        raise RuntimeError("patches_est must have the element count and device of patches")
+    prior_mu = float(prior_mu)
+    if not (math.isfinite(prior_mu) and prior_mu >= 0.0):
+        raise RuntimeError("prior_mu must be finite and >= 0")
     ii, jj, kk = H.idx64(ii), H.idx64(jj), H.idx64(kk)
     lmbda = lmbda.to(device=poses.device, dtype=torch.float32).contiguous()
     E = ii.numel()
@@ -89,10 +111,10 @@ def forward(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t
         if (offs.dtype != torch.int32 or perm.dtype != torch.int32 or groups.dtype != torch.int64 or
                 offs.numel() < E + 1 or perm.numel() < E):
             raise RuntimeError("csr must be update_ops.group_by(kk)'s (offs int32 [E+1], perm int32 [E], groups int64)")
-    H.check(H.lib().dpvo_ba_forward_csr(
+    H.check(H.lib().dpvo_ba_forward_prior(
         H.ptr(poses), H.ptr(patches), num_patches, P, H.ptr(intrinsics), H.ptr(target), H.ptr(weight), H.ptr(lmbda),
-        H.ptr(ii), H.ptr(jj), H.ptr(kk), E, int(t0), int(t1), int(iterations), flags, H.ptr(offs), H.ptr(perm),
-        H.ptr(groups), H.ptr(ws), nbytes, H.ptr(status), H.stream_of(poses)))
+        H.ptr(patches_est), prior_mu, H.ptr(ii), H.ptr(jj), H.ptr(kk), E, int(t0), int(t1), int(iterations), flags,
+        H.ptr(offs), H.ptr(perm), H.ptr(groups), H.ptr(ws), nbytes, H.ptr(status), H.stream_of(poses)))
     last_status = status
     if CHECK_CHOLESKY and not deferred:
         raise_for_status(status.item())

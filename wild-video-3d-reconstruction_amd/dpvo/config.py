@@ -57,6 +57,8 @@ _C.BA_ITERATIONS = 2          # the reference hard-codes 2 (dpvo.py:734)
 _C.CHANNEL_LAST_FMAPS = True  # keep the feature rings channel-contiguous (altcorr fast path)
 _C.EXACT_CORR = False         # True: the bit-exact fp16-chain altcorr instead of the matrix-core kernel
 _C.DEFER_BA_CHECK = True      # BA's Cholesky status read at keyframe()'s host read, not inside update()
+_C.DEPTH_PRIOR_BA = False     # BA honours the per-patch depth prior (patches_est_, reference dpvo/ba.py:151-159)
+_C.DEPTH_PRIOR_MU = 2.0       # its weight mu (the reference hard-codes 0.5 * 4, ba.py:151)
 _C.DEFER_KEYFRAME = False     # keyframe()'s decision applied by the next __call__ (its host read overlaps that frame's encoders)
 
 cfg = _C

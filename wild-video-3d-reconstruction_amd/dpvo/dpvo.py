@@ -455,7 +455,7 @@ class DPVO:
             t0 = max(t0_, t0 or 1)
             fastba.BA(self.poses, self.patches, self.intrinsics, target, weight, self._lmbda, self.pg.ii, self.pg.jj,
                       self.pg.kk, t0, self.n, getattr(self.cfg, "BA_ITERATIONS", 2), csr=kk_groups[1:],
-                      status=self._ba_status if defer else None, keep_status=defer)
+                      status=self._ba_status if defer else None, keep_status=defer, **self._depth_prior())
             if defer:   # keep the first failure until a host read looks at it
                 torch.where(self._ba_fail == 0, self._ba_status, self._ba_fail, out=self._ba_fail)
             m = self.pg.m
@@ -500,6 +500,14 @@ class DPVO:
         # a fresh tensor, as the reference returns (pg.points_ is rewritten by
         # the next update())
         return self.pg.points_[:self.pg.m].clone(), target
+
+    def _depth_prior(self):
+        """BA's depth-prior arguments (cfg.DEPTH_PRIOR_BA: the call the reference
+        holds commented out, dpvo.py:736-745): the persistent patches_est_
+        buffer and a host constant, so nothing new is read inside update()."""
+        if not getattr(self.cfg, "DEPTH_PRIOR_BA", False):
+            return {}
+        return dict(patches_est=self.patches_est, prior_mu=float(getattr(self.cfg, "DEPTH_PRIOR_MU", 2.0)))
 
     def _window_keys(self):
         """True when every edge of the sliding window has n - 64 <= ii, jj < n
@@ -733,7 +741,7 @@ class DPVO:
         target = coords[..., self.P // 2, self.P // 2] + delta.float()
         try:
             fastba.BA(self.poses, self.patches, self.intrinsics, target, weight.float(), self._lmbda, ii, jj, kk, 1,
-                      self.n, 2)
+                      self.n, 2, **self._depth_prior())
         except Exception as e:  # the reference logs and carries on (dpvo.py:499-501)
             print(f"Global BA failed: {e}")
 

@@ -243,6 +243,39 @@ int dpvo_solve_system_assemble(const float* J_i, const float* J_j, const int64_t
                                const float* res, int64_t r, int64_t m, float ep, float lm, double* A, double* b,
                                int* status, void* stream);
 
+/* Loop-closure Sim(3) pose-graph optimisation (optim_utils.py:158-255), native
+ * and in fp64 (csrc/pgo.hip).  poses [n][7] double: camera-to-world SE3 [t, q];
+ * loop_poses [L][8] double: Sim3 [t, q, s] constraints of the loop edges
+ * (loop_ii[l], loop_jj[l]).  State g [n][7] double: tangent coordinates
+ * [tau, phi, sigma] of the world-to-camera Sim3.  Edges: n - 1 chain edges
+ * (i = k, j = k - 1) then the L loops; r = Log(C Exp(g_i) Exp(g_j)^-1).
+ * *status (int32, written at the end of every call): bits 0-3 code (0 ok,
+ * 1 a loop edge with ii == jj, 2 a loop index outside [0, n), 3 the damped
+ * system is not positive definite), bits 4-11 LM iterations run, bits 12-30
+ * the order of the failing leading minor.  2 <= n <= 65536, L <= 65536. */
+size_t dpvo_pgo_workspace_bytes(int64_t n, int64_t L);
+/* res [E][7], Ji, Jj [E][7][7] (exact d r / d g_i, d r / d g_j) and *cost =
+ * mean r^2 (may be NULL) at the state g (NULL: g = Log of the inverted input
+ * poses). */
+int dpvo_pgo_residual(const double* g, const double* poses, const double* loop_poses, const int64_t* loop_ii,
+                      const int64_t* loop_jj, int64_t n, int64_t L, double* res, double* Ji, double* Jj, double* cost,
+                      void* workspace, size_t workspace_bytes, int* status, void* stream);
+/* one damped Gauss-Newton step at g: (J^T J + lm diag(J^T J) + ep I) delta =
+ * -J^T r over the first freen poses (freen = -1: all), the rest of delta
+ * [n][7] zero.  The system is kept as a block skyline and solved by a block
+ * Cholesky sweep; no dense matrix is formed. */
+int dpvo_pgo_step(const double* g, const double* poses, const double* loop_poses, const int64_t* loop_ii,
+                  const int64_t* loop_jj, int64_t n, int64_t L, double ep, double lm, int64_t freen, double* delta,
+                  void* workspace, size_t workspace_bytes, int* status, void* stream);
+/* perform_updates (optim_utils.py:222-255): up to iters (<= 255) LM
+ * iterations enqueued on the stream, accept / reject, lm and the stop rule
+ * decided on the device.  freen as above, or -2: poses up to the largest loop
+ * index (fix_opt_window).  out_sim3 [n][8] = Exp(g)^-1, cost_history [iters]
+ * (NaN in the slots of iterations that did not run). */
+int dpvo_pgo(const double* poses, const double* loop_poses, const int64_t* loop_ii, const int64_t* loop_jj, int64_t n,
+             int64_t L, int iters, double ep, double lmbda, int64_t freen, double* out_sim3, double* cost_history,
+             void* workspace, size_t workspace_bytes, int* status, void* stream);
+
 /* ------------------------------------------------------------------------
  * lietorch -- replaces lietorch_backends (reference lietorch.cpp:286-316)
  * group: 1 = SO3, 3 = SE3 (dispatch.h:16-31); dtype F32 or F64.

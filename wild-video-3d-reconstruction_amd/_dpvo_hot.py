@@ -25,6 +25,7 @@ _vp = ctypes.c_void_p
 _ip = ctypes.c_int
 _fp = ctypes.c_float
 _sz = ctypes.c_size_t
+_dp = ctypes.c_double
 
 # name -> (restype, argtypes)
 _SIGNATURES = {
@@ -58,6 +59,10 @@ _SIGNATURES = {
                                     _ip, _ip, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "dpvo_reproject": (_ip, [_vp, _vp, _ip, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "dpvo_solve_system_assemble": (_ip, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _fp, _fp, _vp, _vp, _vp, _vp]),
+    "dpvo_pgo_workspace_bytes": (_sz, [_i64, _i64]),
+    "dpvo_pgo_residual": (_ip, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "dpvo_pgo_step": (_ip, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _dp, _dp, _i64, _vp, _vp, _sz, _vp, _vp]),
+    "dpvo_pgo": (_ip, [_vp, _vp, _vp, _vp, _i64, _i64, _ip, _dp, _dp, _i64, _vp, _vp, _vp, _sz, _vp, _vp]),
     "dpvo_neighbors_workspace_bytes": (_sz, [_i64]),
     "dpvo_neighbors": (_ip, [_vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "dpvo_lie_forward": (_ip, [_ip, _ip, _ip, _vp, _vp, _vp, _i64, _vp]),

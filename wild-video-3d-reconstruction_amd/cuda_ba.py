@@ -30,6 +30,11 @@ paths: a patch whose prior inverse depth (channel 2, centre pixel of
 ``patches_est``, laid out like ``patches``) is positive and finite is pulled
 towards it with weight ``prior_mu``.  None (or ``prior_mu = 0``) is the plain
 call, bit for bit.
+
+``pgo_residual`` / ``pgo_step`` / ``pgo`` (not in the reference's extension)
+are the loop-closure Sim(3) pose-graph optimisation of optim_utils.py:158-255
+without pypose: exact fp64 Jacobians, a block-skyline Cholesky instead of the
+dense 7n x 7n matrix, the Levenberg-Marquardt loop decided on the device.
 """
 import math
 
@@ -187,3 +192,106 @@ def solve_system(J_Ginv_i, J_Ginv_j, ii, jj, res, ep, lm, freen):
         L = torch.linalg.cholesky(A)
         delta[:m] = torch.cholesky_solve(b[:, None], L)[:, 0].float()
     return [delta.view(n, 7).to(out_dev)]
+
+
+# ---------------------------------------------------------------------------
+# Loop-closure Sim(3) pose-graph optimisation (not in the reference's
+# extension: there it is pypose autograd + solve_system, optim_utils.py:158-255).
+# Native, fp64, device-resident (csrc/pgo.hip): no pypose, no dense 7n x 7n
+# matrix.  poses [n, 7]: camera-to-world SE3 [t, q]; loop_poses [L, 8]: Sim3
+# [t, q, s]; g [n, 7]: tangent coordinates [tau, phi, sigma] of the
+# world-to-camera Sim3 of every pose.  Edge order: the n - 1 chain edges
+# (k, k - 1), then the loops.
+# ---------------------------------------------------------------------------
+def raise_for_pgo_status(word):
+    """the error for a PGO status word (include/dpvo_hot.h); returns the LM iterations run."""
+    word = int(word)
+    code, iters, pivot = word & 15, (word >> 4) & 255, word >> 12
+    if code == 1:
+        raise RuntimeError("pgo: a loop edge with ii == jj (the reference exits the process, ba.cpp:205)")
+    if code == 2:
+        raise RuntimeError("pgo: a loop index outside [0, n)")
+    if code == 3:
+        raise RuntimeError(
+            "linalg.cholesky: The factorization could not be completed because the input is not positive-"
+            f"definite (the leading minor of order {pivot} is not positive-definite).")
+    return iters
+
+
+def _pgo_operands(poses, loop_poses, loop_ii, loop_jj, g=None):
+    H.on_gpu(poses, loop_poses, loop_ii, loop_jj, g)
+    poses = poses.to(torch.float64).contiguous()
+    loop_poses = loop_poses.to(torch.float64).contiguous()
+    loop_ii, loop_jj = H.idx64(loop_ii).view(-1), H.idx64(loop_jj).view(-1)
+    n, L = poses.shape[0], loop_ii.numel()
+    if poses.dim() != 2 or poses.shape[1] != 7 or n < 2:
+        raise RuntimeError("pgo: poses must be [n, 7] (SE3 [t, q]) with n >= 2")
+    if loop_poses.numel() != 8 * L or loop_jj.numel() != L:
+        raise RuntimeError("pgo: loop_poses must be [L, 8] (Sim3 [t, q, s]), loop_ii / loop_jj [L]")
+    if g is not None:
+        g = g.to(torch.float64).contiguous()
+        if g.shape != (n, 7):
+            raise RuntimeError("pgo: g must be [n, 7]")
+    nbytes = H.lib().dpvo_pgo_workspace_bytes(n, L)
+    if nbytes == 0:
+        raise RuntimeError("pgo: n or L out of range (n <= 65536, L <= 65536)")
+    ws = H.empty(nbytes, dtype=torch.uint8, device=poses.device)
+    status = torch.zeros(1, dtype=torch.int32, device=poses.device)
+    return poses, loop_poses, loop_ii, loop_jj, g, n, L, ws, nbytes, status
+
+
+def pgo_workspace_bytes(n, L):
+    """bytes of device workspace one PGO call over n poses and L loops takes"""
+    return int(H.lib().dpvo_pgo_workspace_bytes(int(n), int(L)))
+
+
+def pgo_residual(g, poses, loop_poses, loop_ii, loop_jj):
+    """optim_utils.residual(..., jacobian=True): -> (res [E, 7], Ji [E, 7, 7],
+    Jj [E, 7, 7], iii [E], jjj [E]) in fp64; Ji / Jj are the exact derivatives
+    of res with respect to g[iii] / g[jjj]."""
+    poses, loop_poses, loop_ii, loop_jj, g, n, L, ws, nbytes, status = _pgo_operands(poses, loop_poses, loop_ii,
+                                                                                     loop_jj, g)
+    if g is None:
+        raise RuntimeError("pgo_residual: g missing")
+    E = n - 1 + L
+    res = H.empty((E, 7), dtype=torch.float64, device=poses.device)
+    Ji = H.empty((E, 7, 7), dtype=torch.float64, device=poses.device)
+    Jj = H.empty((E, 7, 7), dtype=torch.float64, device=poses.device)
+    H.check(H.lib().dpvo_pgo_residual(H.ptr(g), H.ptr(poses), H.ptr(loop_poses), H.ptr(loop_ii), H.ptr(loop_jj), n, L,
+                                      H.ptr(res), H.ptr(Ji), H.ptr(Jj), H.ptr(None), H.ptr(ws), nbytes, H.ptr(status),
+                                      H.stream_of(poses)))
+    raise_for_pgo_status(status.item())
+    kk = torch.arange(1, n, device=poses.device)
+    return res, Ji, Jj, torch.cat((kk, loop_ii)), torch.cat((kk - 1, loop_jj))
+
+
+def pgo_step(g, poses, loop_poses, loop_ii, loop_jj, ep, lm, freen):
+    """one damped step at g: the delta [n, 7] (fp64) solve_system gives for
+    pgo_residual's Jacobians, from a block-skyline Cholesky instead of the
+    dense matrix; freen >= 0 solves for the first freen poses only."""
+    poses, loop_poses, loop_ii, loop_jj, g, n, L, ws, nbytes, status = _pgo_operands(poses, loop_poses, loop_ii,
+                                                                                     loop_jj, g)
+    if g is None:
+        raise RuntimeError("pgo_step: g missing")
+    delta = H.empty((n, 7), dtype=torch.float64, device=poses.device)
+    H.check(H.lib().dpvo_pgo_step(H.ptr(g), H.ptr(poses), H.ptr(loop_poses), H.ptr(loop_ii), H.ptr(loop_jj), n, L,
+                                  float(ep), float(lm), max(int(freen), -1), H.ptr(delta), H.ptr(ws), nbytes,
+                                  H.ptr(status), H.stream_of(poses)))
+    raise_for_pgo_status(status.item())
+    return delta
+
+
+def pgo(poses, loop_poses, loop_ii, loop_jj, iters=30, ep=0.0, lmbda=1e-6, fix_opt_window=False):
+    """optim_utils.perform_updates: the whole Levenberg-Marquardt loop in one
+    call -> (sim3 [n, 8] = Exp(g)^-1, cost_history [iters], NaN where an
+    iteration did not run).  One host read (the status word) at the end."""
+    poses, loop_poses, loop_ii, loop_jj, _, n, L, ws, nbytes, status = _pgo_operands(poses, loop_poses, loop_ii,
+                                                                                     loop_jj)
+    iters = int(iters)
+    out = H.empty((n, 8), dtype=torch.float64, device=poses.device)
+    hist = H.empty((iters,), dtype=torch.float64, device=poses.device)
+    H.check(H.lib().dpvo_pgo(H.ptr(poses), H.ptr(loop_poses), H.ptr(loop_ii), H.ptr(loop_jj), n, L, iters, float(ep),
+                             float(lmbda), -2 if fix_opt_window else -1, H.ptr(out), H.ptr(hist), H.ptr(ws), nbytes,
+                             H.ptr(status), H.stream_of(poses)))
+    raise_for_pgo_status(status.item())
+    return out, hist

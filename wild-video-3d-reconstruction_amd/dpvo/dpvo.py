@@ -181,6 +181,30 @@ class DPVO:
         poses = stack([SE3(self.pg.poses_[i]) for i in range(self.n)], dim=0).inv().data.cpu().numpy()
         return poses, torch.as_tensor([self.pg.tstamps_[i] for i in range(self.n)], dtype=torch.float64).numpy()
 
+    # ------------------------------------------------------------------ loop closure (PGO back end)
+    @property
+    def loop_ii(self):
+        return self.pg.loop_ii
+
+    @property
+    def loop_jj(self):
+        return self.pg.loop_jj
+
+    def close_loop(self, i, j, far_rel_pose):
+        """close the loop between keyframes i and j given their measured
+        relative Sim3 far_rel_pose = [t, q, s] (T_j T_i^-1, world-to-camera
+        frames) -- the reference's close_loop after its matcher
+        (loop_closure/long_term.py:253-287): Sim(3) pose-graph optimisation on
+        the GPU, then poses, depths, removed-frame deltas and the point cloud
+        below max(loop_ii) + 1 are corrected in place (PatchGraph.close_loop).
+        update() reads poses_ / patches_ afresh on every call (also when
+        graph-captured: the buffers are written in place), so nothing else is
+        cached.  Retrieval and matching are the caller's: cfg.loop_enabled
+        still raises."""
+        self.flush_keyframe()
+        self.check_ba()
+        return self.pg.close_loop(i, j, far_rel_pose)
+
     # ------------------------------------------------------------------ hot path
     def corr(self, coords, indicies=None, slots=None, order=None):
         """2-level local correlation -> [1, E, 882] (dpvo.py:326-333), one fused launch.

@@ -35,6 +35,8 @@ class PatchGraph:
         self.index_ = torch.zeros(self.N, M, dtype=torch.long, device=dev)
         self.index_map_ = torch.zeros(self.N, dtype=torch.long, device=dev)
         self.delta = {}  # relative poses of removed keyframes
+        self.loop_ii = torch.zeros(0, dtype=torch.long, device=dev)  # loops closed so far (close_loop)
+        self.loop_jj = torch.zeros(0, dtype=torch.long, device=dev)
 
         net_kw = {k: v for k, v in kwargs.items() if k in ("dtype",)}
         self.net = torch.zeros(1, 0, DIM, device=dev, **net_kw)
@@ -76,6 +78,50 @@ class PatchGraph:
         self.poses_[:self.n] = (SE3(self.poses_[:self.n]) * SE3(self.poses_[[0]]).inv()).data
         pops.point_cloud_centre(SE3(self.poses), self.patches[:, :self.m], self.intrinsics, self.ix[:self.m],
                                 out=self.points_[:self.m])
+
+    def close_loop(self, i, j, far_rel_pose, iters=30):
+        """the tail of the reference's loop closer (loop_closure/long_term.py:253-287)
+        for a caller who brings the matcher: far_rel_pose, Sim3 data [t, q, s],
+        is the measured T_j T_i^-1 between the world-to-camera frames i and j
+        (what ransac_umeyama gives for frame i's points matched to frame j's).
+        The earlier loops' constraints are rebuilt from the current poses with
+        scale 1, the Sim(3) pose graph over poses_[:n] is optimised on the GPU
+        (cuda_ba.pgo) and poses, inverse depths and the removed frames' deltas
+        below safe_i = max(loop_ii) + 1 are corrected.  Returns safe_i."""
+        from .loop_closure.optim_utils import SE3_to_Sim3, run_DPVO_PGO_sychronize
+        n, dev = self.n, self.poses_.device
+        far = far_rel_pose.data if hasattr(far_rel_pose, "group_id") else torch.as_tensor(far_rel_pose)
+        far = far.to(device=dev, dtype=torch.float64).reshape(1, 8)
+        loop_poses = far
+        if self.loop_ii.numel():
+            Gi, Gj = SE3(self.poses_[self.loop_ii]), SE3(self.poses_[self.loop_jj])
+            loop_poses = torch.cat((SE3_to_Sim3((Gj * Gi.inv()).data).to(torch.float64), far))
+        loop_ii = torch.cat((self.loop_ii, torch.tensor([int(i)], device=dev)))
+        loop_jj = torch.cat((self.loop_jj, torch.tensor([int(j)], device=dev)))
+        pred_poses = SE3(self.poses_[:n]).inv().data
+        out = run_DPVO_PGO_sychronize(pred_poses, loop_poses, loop_ii, loop_jj, iters=iters)
+        self.loop_ii, self.loop_jj = loop_ii, loop_jj
+        safe_i = out.shape[0]
+        res, s = out.float().split([7, 1], dim=1)
+        s1 = torch.ones(n, device=dev)
+        s1[:safe_i] = s.squeeze(1)
+        self.poses_[:safe_i] = SE3(res).inv().data
+        self.patches_[:safe_i, :, 2] /= s.view(safe_i, 1, 1, 1)
+        self._rescale_deltas(s1)
+        # the cached point cloud follows the poses and depths
+        pops.point_cloud_centre(SE3(self.poses), self.patches[:, :self.m], self.intrinsics, self.ix[:self.m],
+                                out=self.points_[:self.m])
+        return safe_i
+
+    def _rescale_deltas(self, s):
+        """scale the relative poses of removed frames by the scale of the
+        surviving frame their chain of deltas ends on (long_term.py:180-192)"""
+        scale_of = {int(self.tstamps_[k]): s[k] for k in range(self.n)}
+        for t, (t0, dP) in self.delta.items():
+            src = t
+            while src in self.delta:
+                src = self.delta[src][0]
+            self.delta[t] = (t0, dP.scale(scale_of[src]))
 
     def _prior_patch(self, idx, depth):
         """frame idx's patches with the inverse of the median metric depth

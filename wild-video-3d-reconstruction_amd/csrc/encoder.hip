@@ -17,7 +17,8 @@
 //    convolution loads its input (x = relu(relu(IN(y)) + res)); the convolution
 //    that first reads a block output also writes it (the residual of the next
 //    block).  Instance-norm statistics: each producing workgroup writes its
-//    tile's per-channel (sum, sum of squares); every consuming workgroup
+//    tile's per-channel (sum, sum of squares), summed in fp64 and rounded to
+//    fp32 once; every consuming workgroup
 //    reduces all tiles' partials itself, in one fixed order (fp64), while its
 //    weight DMA is in flight.  No cross-workgroup synchronisation, no extra
 //    launch, identical (rstd, -mean rstd) in every workgroup, deterministic.
@@ -81,22 +82,39 @@ __device__ __forceinline__ h8_t xform(h8_t a, const float (&as)[16], bool a_norm
     return o;
 }
 
+// all-reduce of a double over a DPP row (16 lanes), as row16_sum
+template <int CTRL>
+__device__ __forceinline__ double dpp_rot_f64(double v)
+{
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double row16_sum_f64(double s)
+{
+    s += dpp_rot_f64<0x128>(s);
+    s += dpp_rot_f64<0x124>(s);
+    s += dpp_rot_f64<0x122>(s);
+    s += dpp_rot_f64<0x121>(s);
+    return s;
+}
+
 // acc (+ bias) -> fp16 -> out; instance-norm partial sums of the stored
-// values -> part[tile] (sum, sumsq interleaved per channel).
+// values -> part[tile] (sum, sumsq interleaved per channel).  The tile's 128
+// values are summed in fp64 (the squares of fp16 values are exact there) and
+// rounded to fp32 once: the consumer's var = Q / n - mean^2 cancels all but
+// 1 / (1 + R^2) of Q (R = |mean| / std), so every rounding of a partial counts
+// 1 + R^2 times in the variance.  sred: 4 x 2 COUT doubles of LDS.
 template <int COUT>
 __device__ void conv_epilogue(const dpvo_conv_args& e, f4_t (&acc)[2][COUT / 16], int Ho, int Wo, int oy0, int ox0,
-                              int tile, float (*sred)[2 * COUT])
+                              int tile, double* sred)
 {
-    constexpr int NT = COUT / 16;
+    constexpr int NT = COUT / 16, V = 2 * COUT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fq = lane >> 4;
     const bool stats = e.part != nullptr;
     const half_t* bias = (const half_t*)e.bias;
     half_t* out = (half_t*)e.out;
-    float ssum[NT][4], ssq[NT][4];
-#pragma unroll
-    for (int mt = 0; mt < NT; mt++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) ssum[mt][r] = ssq[mt][r] = 0.f;
+    h4_t hv[2][NT];   // the stored values, 0 outside the map
 #pragma unroll
     for (int i = 0; i < 2; i++) {
         const int oy = oy0 + 2 * wave + i, ox = ox0 + (lane & 15);
@@ -112,11 +130,9 @@ __device__ void conv_epilogue(const dpvo_conv_args& e, f4_t (&acc)[2][COUT / 16]
                 half_t h = (half_t)(acc[i][mt][r] + (float)b[r]);
                 if (e.out_scale != 1.f) h = (half_t)((float)h * e.out_scale);
                 v[r] = h;
-                const float s = valid ? (float)h : 0.f;
-                ssum[mt][r] += s;
-                ssq[mt][r] += s * s;
             }
             if (valid) *(h4_t*)(op + co) = v;
+            hv[i][mt] = valid ? v : (h4_t)(half_t)0;
         }
     }
     if (!stats) return;
@@ -124,16 +140,16 @@ __device__ void conv_epilogue(const dpvo_conv_args& e, f4_t (&acc)[2][COUT / 16]
     for (int mt = 0; mt < NT; mt++)
 #pragma unroll
         for (int r = 0; r < 4; r++) {
-            const float s = row16_sum(ssum[mt][r]), q = row16_sum(ssq[mt][r]);
+            const double h0 = (double)(float)hv[0][mt][r], h1 = (double)(float)hv[1][mt][r];
+            const double s = row16_sum_f64(h0 + h1), q = row16_sum_f64(h0 * h0 + h1 * h1);
             if ((lane & 15) == 0) {
-                sred[wave][2 * (mt * 16 + 4 * fq + r)] = s;
-                sred[wave][2 * (mt * 16 + 4 * fq + r) + 1] = q;
+                sred[wave * V + 2 * (mt * 16 + 4 * fq + r)] = s;
+                sred[wave * V + 2 * (mt * 16 + 4 * fq + r) + 1] = q;
             }
         }
     __syncthreads();
-    constexpr int V = 2 * COUT;
     for (int t = tid; t < V; t += EN_THREADS)
-        e.part[(int64_t)tile * V + t] = ((sred[0][t] + sred[1][t]) + sred[2][t]) + sred[3][t];
+        e.part[(int64_t)tile * V + t] = (float)(((sred[t] + sred[V + t]) + sred[2 * V + t]) + sred[3 * V + t]);
 }
 
 // Instance-norm pairs (rstd, -mean rstd) of C channels [co, co + C) of a
@@ -196,8 +212,8 @@ __global__ __launch_bounds__(EN_THREADS) void enc_conv_kernel(EncBatch p)
     constexpr int CP = CIN + 8, KC = CIN / 32, NT = COUT / 16, TAPS = KS * KS;
     __shared__ __attribute__((aligned(16))) half_t sW[TAPS * KC * COUT * 32];
     __shared__ __attribute__((aligned(16))) half_t sX[IH * IW * CP];
-    __shared__ float sred[4][2 * COUT];
-    __shared__ double dred[4 * EN_THREADS];
+    __shared__ double dred[4 * EN_THREADS];   // reduce_stats' slices, then the epilogue's 4 x 2 COUT sums
+    static_assert(4 * 2 * COUT <= 4 * EN_THREADS, "dred holds the epilogue's per-wave sums");
     __shared__ float sss[2][2 * CIN];
 
     const dpvo_conv_args& e = p.e[blockIdx.y];
@@ -288,7 +304,7 @@ __global__ __launch_bounds__(EN_THREADS) void enc_conv_kernel(EncBatch p)
             }
         }
     }
-    conv_epilogue<COUT>(e, acc, p.Ho, p.Wo, oy0, ox0, tile, sred);
+    conv_epilogue<COUT>(e, acc, p.Ho, p.Wo, oy0, ox0, tile, dred);
 }
 
 // conv1 of BasicEncoder4 (7x7, stride 2, pad 3, 3 -> 32) on the uint8 frame,
@@ -318,7 +334,7 @@ __global__ __launch_bounds__(EN_THREADS) void enc_stem_kernel(EncBatch p, const 
     __shared__ __attribute__((aligned(16))) half_t sA[EN_TH * EN_TW * ST_KP];
     __shared__ __attribute__((aligned(16))) half_t sW[32 * ST_K];
     __shared__ half_t sI[3 * ST_IH * ST_IW];
-    __shared__ float sred[4][64];
+    __shared__ double sred[4 * 64];
 
     const dpvo_conv_args& e = p.e[blockIdx.y];
     const int tile = blockIdx.x;

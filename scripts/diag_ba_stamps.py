@@ -1,4 +1,4 @@
-"""Where the BA patch kernel's time goes (csrc/fastba.hip bd_patch_kernel,
+"""Where the BA patch kernel's time goes (csrc/fastba_det.hip bd_patch_kernel,
 DPVO_STAMPS build in diag/libdpvo_hot.so): per-wave cycles by phase, on the
 bench's steady-state tracker (C2 by default), from the last <APPLY, HESS>
 launch of one update()."""

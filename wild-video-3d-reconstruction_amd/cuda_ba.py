@@ -2,7 +2,8 @@
 
 Same module name, functions and argument meaning as dpvo/fastba/ba.cpp:236-241
 (imported by dpvo/fastba/ba.py:2); the work runs in libdpvo_hot.so
-(csrc/fastba.hip) on the current HIP stream.
+(csrc/fastba.hip: entry points and dispatch; fastba_det.hip and
+fastba_atomic.hip: the solver paths) on the current HIP stream.
 
 ``CHECK_CHOLESKY`` (default True) keeps the reference's behaviour of raising
 when the Schur system is not positive definite (torch::linalg::cholesky in

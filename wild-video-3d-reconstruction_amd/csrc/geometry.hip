@@ -102,34 +102,42 @@ __global__ __launch_bounds__(256) void point_cloud_kernel(const float* __restric
                                                          float* __restrict__ out)
 {
     const int64_t PP = (int64_t)P * P, centre = (P / 2) * P + P / 2;
+    // centre_only is the pixel range [centre, centre + 1) of the same loop, and
+    // the loop is kept as one instance (no unrolling): the centre is then the
+    // full cloud's pixel before its division by w.  Two copies of the body were
+    // contracted into different FMAs, 10 ulp apart where the sum cancels.
+    const int64_t q0 = centre_only ? centre : 0, q1 = centre_only ? centre + 1 : PP;
     for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < m; k += (int64_t)gridDim.x * blockDim.x) {
         const int64_t f = ix[k];
-        const float* K = intr + f * 4;
         const float* pa = patches + k * 3 * PP;
-        if (centre_only) {
-            // every operand load issued before the arithmetic (G3::load normalizes)
-            float rp[7], kv[4], c[3];
-            __builtin_amdgcn_sched_barrier(0);
+        // every operand load of the first pixel issued before the arithmetic (G3::load normalizes)
+        float rp[7], kv[4], c[3];
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int t = 0; t < 7; t++) rp[t] = poses[f * 7 + t];
+        for (int t = 0; t < 7; t++) rp[t] = poses[f * 7 + t];
 #pragma unroll
-            for (int t = 0; t < 4; t++) kv[t] = K[t];
+        for (int t = 0; t < 4; t++) kv[t] = intr[f * 4 + t];
 #pragma unroll
-            for (int t = 0; t < 3; t++) c[t] = pa[t * PP + centre];
-            __builtin_amdgcn_sched_barrier(0);
-            const G3 g = G3::load(rp).inv();
+        for (int t = 0; t < 3; t++) c[t] = pa[t * PP + q0];
+        __builtin_amdgcn_sched_barrier(0);
+        const G3 g = G3::load(rp).inv();
+        int64_t q = q0;
+#pragma unroll 1
+        for (;;) {
             const float X0[4] = {(c[0] - kv[2]) / kv[0], (c[1] - kv[3]) / kv[1], 1.0f, c[2]};
             float X1[4];
             g.act4(X0, X1);
-            out[k * 3 + 0] = X1[0] / X1[3];
-            out[k * 3 + 1] = X1[1] / X1[3];
-            out[k * 3 + 2] = X1[2] / X1[3];
-        } else {
-            const G3 g = G3::load(poses + f * 7).inv();
-            for (int64_t q = 0; q < PP; q++) {
-                const float X0[4] = {(pa[q] - K[2]) / K[0], (pa[PP + q] - K[3]) / K[1], 1.0f, pa[2 * PP + q]};
-                g.act4(X0, out + (k * PP + q) * 4);
+            if (centre_only) {
+                out[k * 3 + 0] = X1[0] / X1[3];
+                out[k * 3 + 1] = X1[1] / X1[3];
+                out[k * 3 + 2] = X1[2] / X1[3];
+            } else {
+                float* o = out + (k * PP + q) * 4;
+                o[0] = X1[0]; o[1] = X1[1]; o[2] = X1[2]; o[3] = X1[3];
             }
+            if (++q >= q1) break;
+#pragma unroll
+            for (int t = 0; t < 3; t++) c[t] = pa[t * PP + q];
         }
     }
 }

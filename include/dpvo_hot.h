@@ -276,6 +276,31 @@ int dpvo_pgo(const double* poses, const double* loop_poses, const int64_t* loop_
              int64_t L, int iters, double ep, double lmbda, int64_t freen, double* out_sim3, double* cost_history,
              void* workspace, size_t workspace_bytes, int* status, void* stream);
 
+/* Loop-closure alignment (optim_utils.py:64-150): the Sim(3) y ~ s R x + t
+ * between two matched point clouds src, dst [N][3] double, by RANSAC over
+ * 3-point Umeyama models and a least-squares refit on the winner's inliers,
+ * native and in fp64 (csrc/align.hip).  The samples are the caller's
+ * (int32 [H][3], indices into the N points); the device draws no random
+ * numbers.  out_counts [H] int32: the points with |s R x + t - y| < threshold
+ * under hypothesis h, or -1 when its sample repeats an index, leaves [0, N) or
+ * is degenerate (fewer than 2 singular values of its covariance above
+ * DBL_EPSILON, the reference's rule).  Winner: the first hypothesis with a
+ * count > early_exit (early_exit < 0: never), else the first with the largest
+ * count -- the reference's sequential loop on the same samples.  out_mask [N]
+ * uint8: the winner's inliers; out_sim3 [8] double [t, q (x y z w), s]: the
+ * refit over them (NaN unless the code is 0); out_info [4] int32: {code,
+ * winner, the winner's count, the refit's point count}, code 0 ok, 1 no valid
+ * hypothesis, 2 degenerate refit.  Fixed-order sums: bitwise repeatable.
+ * 3 <= N <= 2^24, 1 <= H <= 2^20, threshold finite and > 0.  No host read. */
+size_t dpvo_sim3_workspace_bytes(int64_t N, int64_t H);
+int dpvo_sim3_ransac(const double* src, const double* dst, int64_t N, const int* samples, int64_t H, double threshold,
+                     int early_exit, double* out_sim3, int* out_counts, unsigned char* out_mask, int* out_info,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* the refit alone, over the points with mask[p] != 0 (mask NULL: all N);
+ * out_info = {code (0 or 2), -1, 0, point count}. */
+int dpvo_sim3_umeyama(const double* src, const double* dst, int64_t N, const unsigned char* mask, double* out_sim3,
+                      int* out_info, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * lietorch -- replaces lietorch_backends (reference lietorch.cpp:286-316)
  * group: 1 = SO3, 3 = SE3 (dispatch.h:16-31); dtype F32 or F64.

@@ -63,6 +63,9 @@ _SIGNATURES = {
     "dpvo_pgo_residual": (_ip, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "dpvo_pgo_step": (_ip, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _dp, _dp, _i64, _vp, _vp, _sz, _vp, _vp]),
     "dpvo_pgo": (_ip, [_vp, _vp, _vp, _vp, _i64, _i64, _ip, _dp, _dp, _i64, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "dpvo_sim3_workspace_bytes": (_sz, [_i64, _i64]),
+    "dpvo_sim3_ransac": (_ip, [_vp, _vp, _i64, _vp, _i64, _dp, _ip, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dpvo_sim3_umeyama": (_ip, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dpvo_neighbors_workspace_bytes": (_sz, [_i64]),
     "dpvo_neighbors": (_ip, [_vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "dpvo_lie_forward": (_ip, [_ip, _ip, _ip, _vp, _vp, _vp, _i64, _vp]),

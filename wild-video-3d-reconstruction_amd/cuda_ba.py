@@ -36,6 +36,11 @@ call, bit for bit.
 are the loop-closure Sim(3) pose-graph optimisation of optim_utils.py:158-255
 without pypose: exact fp64 Jacobians, a block-skyline Cholesky instead of the
 dense 7n x 7n matrix, the Levenberg-Marquardt loop decided on the device.
+
+``ransac_sim3`` / ``umeyama`` (not in the reference's extension) are the
+point-cloud alignment of optim_utils.py:64-150 without numba or a host copy:
+RANSAC over the caller's 3-point samples and the Umeyama refit, fp64, bitwise
+repeatable (csrc/align.hip).
 """
 import math
 
@@ -296,3 +301,62 @@ def pgo(poses, loop_poses, loop_ii, loop_jj, iters=30, ep=0.0, lmbda=1e-6, fix_o
                              H.ptr(status), H.stream_of(poses)))
     raise_for_pgo_status(status.item())
     return out, hist
+
+
+# ---------------------------------------------------------------------------
+# Loop-closure alignment (not in the reference's extension: there it is numba
+# on the host, optim_utils.py:64-150).  Native, fp64, device-resident
+# (csrc/align.hip).  src, dst [N, 3]: matched points, y ~ s R x + t; sim3 [8]:
+# [t, q (x y z w), s]; info [4] int32: {code, winner, winner's count, refit
+# point count}, code 0 ok, 1 no valid hypothesis, 2 degenerate refit.
+# ---------------------------------------------------------------------------
+def _align_operands(name, src, dst):
+    H.on_gpu(src, dst)
+    src, dst = src.to(torch.float64).contiguous(), dst.to(torch.float64).contiguous()
+    if src.dim() != 2 or src.shape[1] != 3 or dst.shape != src.shape or dst.device != src.device:
+        raise RuntimeError(f"{name}: src and dst must be [N, 3] on one device")
+    return src, dst, src.shape[0]
+
+
+def ransac_sim3(src, dst, samples, threshold, early_exit=100):
+    """optim_utils.ransac_umeyama on the caller's samples (any integer tensor
+    [H, 3]; optim_utils.draw_samples gives the reference's sequence) ->
+    (sim3 [8], counts [H] int32, mask [N] bool, info [4] int32), all on the
+    device, no host read.  counts[h] = -1 for an invalid or degenerate sample;
+    early_exit < 0 gives the first hypothesis with the largest count."""
+    src, dst, N = _align_operands("ransac_sim3", src, dst)
+    H.on_gpu(samples)
+    if torch.is_floating_point(samples) or samples.dim() != 2 or samples.shape[1] != 3:
+        raise RuntimeError("ransac_sim3: samples must be an integer tensor [H, 3]")
+    samples = samples.to(device=src.device, dtype=torch.int32).contiguous()
+    nh = samples.shape[0]
+    dev = src.device
+    sim3 = H.empty(8, dtype=torch.float64, device=dev)
+    counts = H.empty(nh, dtype=torch.int32, device=dev)
+    mask = H.empty(N, dtype=torch.bool, device=dev)
+    info = H.empty(4, dtype=torch.int32, device=dev)
+    nbytes = H.lib().dpvo_sim3_workspace_bytes(N, nh)
+    ws = H.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    H.check(H.lib().dpvo_sim3_ransac(H.ptr(src), H.ptr(dst), N, H.ptr(samples), nh, float(threshold), int(early_exit),
+                                     H.ptr(sim3), H.ptr(counts), H.ptr(mask), H.ptr(info), H.ptr(ws), nbytes,
+                                     H.stream_of(src)))
+    return sim3, counts, mask, info
+
+
+def umeyama(src, dst, mask=None):
+    """optim_utils.umeyama_alignment over the rows with mask (bool / uint8 [N];
+    None: all) -> (sim3 [8], info [4] int32) on the device, no host read."""
+    src, dst, N = _align_operands("umeyama", src, dst)
+    if mask is not None:
+        H.on_gpu(mask)
+        if mask.numel() != N or mask.dtype not in (torch.bool, torch.uint8) or mask.device != src.device:
+            raise RuntimeError("umeyama: mask must be a bool / uint8 tensor [N] on the points' device")
+        mask = mask.contiguous().view(-1)
+    dev = src.device
+    sim3 = H.empty(8, dtype=torch.float64, device=dev)
+    info = H.empty(4, dtype=torch.int32, device=dev)
+    nbytes = H.lib().dpvo_sim3_workspace_bytes(N, 0)
+    ws = H.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    H.check(H.lib().dpvo_sim3_umeyama(H.ptr(src), H.ptr(dst), N, H.ptr(mask), H.ptr(sim3), H.ptr(info), H.ptr(ws),
+                                      nbytes, H.stream_of(src)))
+    return sim3, info

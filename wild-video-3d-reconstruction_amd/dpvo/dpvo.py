@@ -205,6 +205,25 @@ class DPVO:
         self.check_ba()
         return self.pg.close_loop(i, j, far_rel_pose)
 
+    def close_loop_from_points(self, i, j, i_pts, j_pts, **kwargs):
+        """close_loop for matched 3-D points of the keyframes i and j (each in
+        its own camera frame): the depth gate, RANSAC + Umeyama on the GPU and
+        the inlier gates of long_term.py:218-251, then close_loop.  False (and
+        an untouched patch graph) when a gate fails, else safe_i
+        (PatchGraph.close_loop_from_points)."""
+        self.flush_keyframe()
+        self.check_ba()
+        return self.pg.close_loop_from_points(i, j, i_pts, j_pts, **kwargs)
+
+    def close_loop_from_tracks(self, i, j, tracks_i, tracks_j, match_i, match_j, **kwargs):
+        """close_loop for a caller who brings a detector and a matcher: the
+        three-frame keypoint tracks of both keyframes and the matcher's index
+        pairs; triangulation, alignment and the pose-graph optimisation run
+        here (PatchGraph.close_loop_from_tracks)."""
+        self.flush_keyframe()
+        self.check_ba()
+        return self.pg.close_loop_from_tracks(i, j, tracks_i, tracks_j, match_i, match_j, **kwargs)
+
     # ------------------------------------------------------------------ hot path
     def corr(self, coords, indicies=None, slots=None, order=None):
         """2-level local correlation -> [1, E, 882] (dpvo.py:326-333), one fused launch.

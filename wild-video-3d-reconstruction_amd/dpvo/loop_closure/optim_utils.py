@@ -2,8 +2,10 @@
 
 The names are the reference's; the work is not pypose's: the Sim(3)
 pose-graph optimisation runs in ``cuda_ba.pgo_residual`` / ``pgo_step`` /
-``pgo`` (csrc/pgo.hip, fp64 on the GPU), the point-cloud alignment is plain
-numpy.  Poses are camera-to-world SE3 ``[t, q]``, Sim3 data is ``[t, q, s]``;
+``pgo`` (csrc/pgo.hip, fp64 on the GPU); the point-cloud alignment is
+``cuda_ba.ransac_sim3`` / ``umeyama`` (csrc/align.hip, fp64 on the GPU) behind
+``ransac_umeyama_gpu``, with the plain-numpy functions of the reference's names
+kept beside it.  Poses are camera-to-world SE3 ``[t, q]``, Sim3 data is ``[t, q, s]``;
 arguments may be this package's ``lietorch`` groups or plain tensors.
 """
 import numpy as np
@@ -138,3 +140,31 @@ def ransac_umeyama(src_points, dst_points, iterations=1, threshold=0.1, rng=None
         if inliers > 100:
             break
     return best[0], best[1], best[2], best_inliers
+
+
+# ---- the same alignment on the device (csrc/align.hip)
+def draw_samples(N, iterations, rng=None):
+    """the 3-point samples ransac_umeyama draws from this Generator (or seed),
+    in its order: `iterations` calls of rng.choice(N, 3, replace=False) ->
+    int64 [iterations, 3]"""
+    rng = np.random.default_rng(rng)
+    return np.stack([rng.choice(N, 3, replace=False) for _ in range(iterations)]).astype(np.int64)
+
+
+def ransac_umeyama_gpu(src_points, dst_points, iterations=400, threshold=0.5, rng=None, early_exit=100):
+    """ransac_umeyama on the device: src_points / dst_points [N, 3] GPU tensors
+    (fp32 or fp64), the samples of draw_samples(N, iterations, rng) -> (Sim3
+    data [1, 8] fp64 on the device, inliers), or (None, 0) when no sample
+    worked or the refit is degenerate.  With the same Generator it returns
+    what ransac_umeyama returns (the reference stops at the first sample with
+    more than early_exit = 100 inliers; early_exit < 0: the best of all).
+    One host read, of the four status words."""
+    N = src_points.shape[0]
+    if N < 3:
+        return None, 0
+    samples = torch.from_numpy(draw_samples(N, iterations, rng)).to(src_points.device)
+    sim3, _, _, info = cuda_ba.ransac_sim3(src_points, dst_points, samples, threshold, early_exit=early_exit)
+    code, _, inliers, _ = info.tolist()
+    if code != 0:
+        return None, 0
+    return sim3.view(1, 8), int(inliers)

@@ -113,6 +113,59 @@ class PatchGraph:
                                 out=self.points_[:self.m])
         return safe_i
 
+    def close_loop_from_points(self, i, j, i_pts, j_pts, iterations=400, threshold=0.5, min_inliers=30,
+                               max_depth=20.0, rng=None):
+        """the reference's close_loop from its depth gate on
+        (loop_closure/long_term.py:218-287) for a caller who brings matched
+        3-D points: i_pts [N, 3] in camera i's frame and j_pts [N, 3], the
+        same points in camera j's frame (GPU tensors, row k matched to row k).
+        Pairs where either point lies at z >= max_depth are dropped; the
+        Sim(3) between the clouds comes from RANSAC + Umeyama on the device
+        (ransac_umeyama_gpu, `iterations` samples from the numpy Generator or
+        seed rng); with at least min_inliers pairs and inliers the loop is
+        closed: returns close_loop(i, j, far_rel_pose), the index safe_i.
+        Otherwise returns False and leaves the patch graph untouched."""
+        from .loop_closure.optim_utils import ransac_umeyama_gpu
+        i_pts, j_pts = torch.as_tensor(i_pts), torch.as_tensor(j_pts)
+        if i_pts.dim() != 2 or i_pts.shape[1] != 3 or j_pts.shape != i_pts.shape:
+            raise RuntimeError("close_loop_from_points: i_pts and j_pts must both be [N, 3]")
+        near = (i_pts[:, 2] < max_depth) & (j_pts[:, 2] < max_depth)
+        i_pts, j_pts = i_pts[near], j_pts[near]
+        if i_pts.shape[0] < min_inliers:
+            return False
+        far_rel_pose, inliers = ransac_umeyama_gpu(i_pts, j_pts, iterations=iterations, threshold=threshold, rng=rng)
+        if far_rel_pose is None or inliers < min_inliers:
+            return False
+        return self.close_loop(i, j, far_rel_pose)
+
+    def close_loop_from_tracks(self, i, j, tracks_i, tracks_j, match_i, match_j, ba_iterations=6, max_residual=2.0,
+                               **kwargs):
+        """close_loop for a caller who brings a detector and a matcher and
+        nothing else (loop_closure/long_term.py:210-287).  tracks_i: (kps_prev,
+        kps, kps_next), each [n_i, 2], the full-resolution pixel positions of
+        frame i's keypoints in the keyframes i - 1, i, i + 1; tracks_j the same
+        for frame j; match_i, match_j [K]: the matcher's index pairs (keypoint
+        match_i[k] of frame i is keypoint match_j[k] of frame j).  Both frames
+        are triangulated (loop_closure.triangulate_keypoints), a match survives
+        when both of its keypoints were kept, and the matched points go to
+        close_loop_from_points (whose keywords pass through)."""
+        from .loop_closure.long_term import triangulate_keypoints
+        dev = self.poses_.device
+        pts_i, keep_i = triangulate_keypoints(self, i, *tracks_i, iterations=ba_iterations, max_residual=max_residual)
+        pts_j, keep_j = triangulate_keypoints(self, j, *tracks_j, iterations=ba_iterations, max_residual=max_residual)
+        match_i = torch.as_tensor(match_i, device=dev).long().view(-1)
+        match_j = torch.as_tensor(match_j, device=dev).long().view(-1)
+        if match_i.numel() != match_j.numel():
+            raise RuntimeError("close_loop_from_tracks: match_i and match_j must have one length")
+        # the reference compacts both clouds by their keep masks and the matcher then indexes the
+        # compacted clouds; with matches over the original keypoints that is: position of the
+        # keypoint among the kept ones = cumsum(keep) - 1
+        both = keep_i[match_i] & keep_j[match_j]
+        slot_i, slot_j = keep_i.cumsum(0) - 1, keep_j.cumsum(0) - 1
+        i_pts = pts_i[keep_i][slot_i[match_i[both]]]
+        j_pts = pts_j[keep_j][slot_j[match_j[both]]]
+        return self.close_loop_from_points(i, j, i_pts, j_pts, **kwargs)
+
     def _rescale_deltas(self, s):
         """scale the relative poses of removed frames by the scale of the
         surviving frame their chain of deltas ends on (long_term.py:180-192)"""

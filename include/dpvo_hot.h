@@ -488,7 +488,12 @@ typedef struct dpvo_rowgemm_args {
     const void* head_w; const void* head_b; void* head_out;
     void* out32; int64_t ldo32; void* out16; int64_t ldo16;
     int flags;
-    const int64_t* M_dev;   /* optional: row count read on the device (M is then the upper bound) */
+    /* optional: row count read on the device (M is then the upper bound).  In
+     * dpvo_rowgemm with DPVO_RG_WKB and K = 384 or 896 a device row count also
+     * selects 32-row tiles, meant for *M_dev << M (SoftAgg's group GEMMs): each
+     * tile re-streams the whole W from L2, so with a count close to M this is
+     * correct but much slower than the 128-row kernel -- pass M alone then. */
+    const int64_t* M_dev;
 } dpvo_rowgemm_args;
 int dpvo_rowgemm(const dpvo_rowgemm_args* args, void* stream);
 

@@ -1,4 +1,4 @@
-"""Where the c1 / c2 chain's time goes (rowchain5_kernel<RES>, csrc/rowgemm.hip,
+"""Where the c1 / c2 chain's time goes (rowchain5_kernel<RES>, csrc/rowgemm_kblocked.hip,
 DPVO_STAMPS build in diag/libdpvo_hot.so): per tile, cycles in the GEMM1
 k-loop (with the previous tile's residual epilogue overlapped), the GEMM1 ->
 y tile write, GEMM2, the y-tile write, at C3 shapes (E = 95,424 gathered rows).

@@ -1,4 +1,4 @@
-"""Where rowgemm5's k-loop time goes (csrc/rowgemm.hip, DPVO_STAMPS build in
+"""Where rowgemm5's k-loop time goes (csrc/rowgemm_kblocked.hip, DPVO_STAMPS build in
 diag/libdpvo_hot.so): per k-step cycles waiting at the barrier, waiting for
 the step's W / A registers (vmcnt), and issuing the step, plus the row
 epilogue per tile -- E = 95,424 rows.  Since round 6 the SoftAgg pair (K =

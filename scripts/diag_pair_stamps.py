@@ -1,4 +1,4 @@
-"""Where the resident-A pair's time goes (rowpair6 in csrc/rowgemm.hip,
+"""Where the resident-A pair's time goes (rowpair6 in csrc/rowgemm_kblocked.hip,
 DPVO_STAMPS build in diag/libdpvo_hot.so): per tile, the cycles of pass 0's
 barrier waits and the rest of its k-steps, the pass-0 row epilogue, pass 1
 (from LDS), and the pass-1 epilogue -- for the SoftAgg pair on fp16 rows and

@@ -433,6 +433,75 @@ def test_rowchain_gated_pre():
         check_epilogue(f"rowchain_gated_pre M={M}", r, M, o32, o16, None)
 
 
+def same_outputs(ref, got, what):
+    for name, r, g in zip(("out32", "out16", "head_out"), ref, got):
+        assert (r is None) == (g is None)
+        if r is not None:
+            assert same(g, r, f"{what} {name}")
+
+
+@pytest.mark.parametrize("act1", [R.SIGMOID, 0])
+def test_rowchain3_run_time_first_activation(act1):
+    """dpvo_rowchain3 with a first activation that is not ReLU (K1 = 64): the
+    three-GEMM kernel that reads the activation from the flags at run time,
+    bit for bit the composition test_gpu_rowgemm uses for ReLU -- rowchain
+    (LN | LN_RELU) writing fp16 rows, then rowgemm (RES | LN) with the gather."""
+    import update_ops as U
+    _, t = EX(64)
+    W3, b3 = EX(384)[1]["W1"], EX(384)[1]["b1"]
+    kw = dict(flags=R.RES | R.LN, res32=t["res32"], res16=t["res16"], res16_idx=t["res16_idx"], ln=t["ln"], want32=True)
+    _, h, _ = U.rowchain(t["A"], t["W1"], t["b1"], t["W2"], t["b2"], flags1=act1, flags=R.LN | R.LN_RELU, ln=t["ln"])
+    ref = U.rowgemm(h, W3, b3, **kw)
+    got = U.rowchain(t["A"], t["W1"], t["b1"], W3, b3, flags1=act1, mid=(t["W2"], t["b2"], t["ln"]), **kw)
+    same_outputs(ref, got, f"rowchain3 act1={act1}")
+
+
+@pytest.mark.parametrize("case", ["gate_ln", "gate_heads"])
+@pytest.mark.parametrize("act1", [R.SIGMOID, 0])
+def test_rowchain_gated_run_time_first_activation(act1, case):
+    """dpvo_rowchain_gated with a first activation that is not ReLU (K1 = 64):
+    the gated kernels that read it from the flags at run time, bit for bit the
+    gate rowgemm (SIGMOID) followed by rowchain(gate16 = its output)."""
+    import update_ops as U
+    d, t = EX(64)
+    flags, _, kk = epi_kwargs(case, d, t)
+    kk.pop("gate16")
+    chain = functools.partial(U.rowchain, t["A"], t["W1"], t["b1"], t["W2"], t["b2"], flags1=act1, flags=flags,
+                              want32=True, **kk)
+    _, g16, _ = U.rowgemm(t["A"], t["Wb"], t["bb"], flags=R.SIGMOID)
+    same_outputs(chain(gate16=g16), chain(gate=(t["Wb"], t["bb"])), f"rowchain_gated {case} act1={act1}")
+
+
+@pytest.mark.parametrize("K", [128, 64])
+def test_rowgemm_pair_rows_8_byte_aligned(K):
+    """dpvo_rowgemm_pair writing out16 rows that are only 8-byte aligned
+    (ldo16 = 388): the two-rows-per-pass store path of rowpair6 (K = 128) and
+    rowgemm5 DUAL (K = 64), which the shim's 384-wide outputs never take.
+    Bit for bit the shim's outputs; padding columns and rows past M untouched."""
+    import ctypes
+
+    import _dpvo_hot as H
+    import update_ops as U
+    _, t = EX(K)
+    A = t["A"]
+    ops = ((weight(t, "kb", "W1"), t["b1"]), (weight(t, "kb", "Wb"), t["bb"]))
+    want = U.rowgemm_pair(A, ops[0][0], ops[0][1], ops[1][0], ops[1][1])
+    outs, args = [], []
+    for W, b in ops:
+        o = full16(ROWS + PAD, R.WIDTH + 4)
+        a = U.RowGemmArgs()
+        a.A, a.lda, a.a_rows, a.W, a.K, a.N, a.bias = A.data_ptr(), A.stride(0), ROWS, W.data_ptr(), K, R.WIDTH, b.data_ptr()
+        a.zero_row, a.M, a.flags, a.out16, a.ldo16 = U.zero_row(A.device, K).data_ptr(), ROWS, U.WKB, o.data_ptr(), o.stride(0)
+        outs.append(o)
+        args.append(a)
+    assert outs[0].stride(0) == 388 and outs[0].data_ptr() % 16 == 0
+    H.check(H.lib().dpvo_rowgemm_pair(ctypes.byref(args[0]), ctypes.byref(args[1]), H.stream_of(A)))
+    for o, w, name in zip(outs, want, "fg"):
+        assert same(o[:ROWS, :R.WIDTH], w, f"pair K={K} ldo16=388 {name}")
+        untouched(o[ROWS:], S16, f"pair ldo16=388 {name} rows past M")
+        untouched(o[:, R.WIDTH:], S16, f"pair ldo16=388 {name} padding")
+
+
 # ---------------------------------------------------------------------------
 # more 128-row tiles than twice the compute units: once per kernel, K <= 384
 @pytest.mark.parametrize("kernel", ["rowgemm3", "rowgemm5", "narrow", "pair3", "pair5", "pair6", "pair_pre",

@@ -6,6 +6,8 @@ Update.forward (dpvo/net.py:82-85).  Inference only (no autograd); the
 dpvo.blocks / dpvo.net mirrors call these under ``torch.no_grad`` and keep a
 torch composition for training.  Like the other shims there is no CPU path.
 """
+import ctypes as _ct
+
 import torch
 
 import _dpvo_hot as H
@@ -125,31 +127,9 @@ def rowchain(A, W1, b1, W2, b2, flags1=None, flags=0, a_idx=None, M=None, res32=
     head_out = H.empty(M, 4, dtype=torch.float16, device=dev) if heads is not None else None
     if res16_idx is not None:
         res16_idx = H.idx64(res16_idx)
-    g1 = RowGemmArgs()
-    g1.A, g1.lda, g1.a_idx, g1.a_rows = _p(A), A.stride(0), _p(a_idx), A.shape[0]
-    g1.W, g1.K, g1.N, g1.bias, g1.zero_row = _p(W1), Kp, WIDTH, _p(b1), _p(zero_row(dev, Kp))
-    g1.M, g1.flags = M, int(flags1)
-    if M_dev is not None:
-        if M_dev.dtype != torch.int64 or not M_dev.is_cuda:
-            raise RuntimeError("rowchain: M_dev must be a device int64 scalar")
-        g1.M_dev = M_dev.data_ptr()
-    g2 = RowGemmArgs()
-    g2.W, g2.K, g2.N, g2.bias = _p(W2), WIDTH, WIDTH, _p(b2)
-    g2.res32, g2.ldr = _p(res32), (res32.stride(0) if res32 is not None else 0)
-    g2.res16, g2.res16_idx, g2.gate16 = _p(res16), _p(res16_idx), _p(gate16)
-    if ln is not None:
-        g2.ln_g, g2.ln_b, g2.ln_eps = _p(ln[0]), _p(ln[1]), float(ln[2])
-    if heads is not None:
-        g2.head_w, g2.head_b, g2.head_out = _p(heads[0]), _p(heads[1]), _p(head_out)
-    g2.out32, g2.ldo32 = _p(out32), (out32.stride(0) if out32 is not None else 0)
-    g2.out16, g2.ldo16 = _p(out16), (out16.stride(0) if out16 is not None else 0)
-    g2.flags = int(flags)
-    for t, nm in ((res32, "res32"), (out32, "out32")):
-        if t is not None and (t.dtype != torch.float32 or t.stride(1) != 1):
-            raise RuntimeError(f"rowchain: {nm} must be fp32 with contiguous rows")
-    for t, nm in ((res16, "res16"), (gate16, "gate16")):
-        if t is not None and (t.dtype != torch.float16 or not t.is_contiguous() or t.shape[-1] != WIDTH):
-            raise RuntimeError(f"rowchain: {nm} must be contiguous fp16 [*, 384]")
+    g1 = _gemm_args("rowchain", W1, Kp, b1, A=A, a_idx=a_idx, M=M, flags=flags1, M_dev=M_dev)
+    g2 = _gemm_args("rowchain", W2, WIDTH, b2, flags=flags, res32=res32, res16=res16, res16_idx=res16_idx,
+                    gate16=gate16, ln=ln, heads=heads, head_out=head_out, out32=out32, out16=out16)
     if gate is not None:
         Wg, bg = gate
         H.on_gpu(Wg, bg)
@@ -158,8 +138,7 @@ def rowchain(A, W1, b1, W2, b2, flags1=None, flags=0, a_idx=None, M=None, res32=
             raise RuntimeError("rowchain: gate W must be fp16 contiguous of W1's shape, bias fp16")
         if gate16 is not None:
             raise RuntimeError("rowchain: pass either gate16 or gate, not both")
-        gg = RowGemmArgs()
-        gg.W, gg.K, gg.N, gg.bias = _p(Wg), Kp, WIDTH, _p(bg)
+        gg = _gemm_args("rowchain", Wg, Kp, bg)
         if pre is not None:
             a32, pb16, pbi, pc16, pci, pln = pre
             H.on_gpu(a32, pb16, pc16, pln[0], pln[1])
@@ -185,10 +164,7 @@ def rowchain(A, W1, b1, W2, b2, flags1=None, flags=0, a_idx=None, M=None, res32=
         Wm = kblock(Wm)
         if Wm.dtype != torch.float16 or bm.dtype != torch.float16 or _kb_K(Wm) != WIDTH:
             raise RuntimeError("rowchain: the middle W must be a contiguous fp16 [384, 384], bias fp16")
-        gm = RowGemmArgs()
-        gm.W, gm.K, gm.N, gm.bias = _p(Wm), WIDTH, WIDTH, _p(bm)
-        gm.ln_g, gm.ln_b, gm.ln_eps = _p(lnm[0]), _p(lnm[1]), float(lnm[2])
-        gm.flags = LN | LN_RELU
+        gm = _gemm_args("rowchain", Wm, WIDTH, bm, flags=LN | LN_RELU, ln=lnm)
         H.check(H.lib().dpvo_rowchain3(_ct.byref(g1), _ct.byref(gm), _ct.byref(g2), H.stream_of(A)))
     else:
         H.check(H.lib().dpvo_rowchain(_ct.byref(g1), _ct.byref(g2), H.stream_of(A)))
@@ -306,10 +282,9 @@ def gather_rows(x, idx, dtype=None):
 
 
 # ---------------------------------------------------------------------------
-# full-row fused GEMM (csrc/rowgemm.hip)
+# full-row fused GEMM (csrc/rowgemm.hip: the entry points; the kernels in
+# csrc/rowgemm_kblocked.hip and csrc/rowgemm_rowmajor.hip)
 # ---------------------------------------------------------------------------
-import ctypes as _ct  # noqa: E402
-
 RELU, SIGMOID, RES, GATE, LN, LN_RELU, HEADS, WKB = 1, 2, 4, 8, 16, 32, 64, 128
 WIDTH = 384
 
@@ -378,6 +353,49 @@ def _p(t):
     return t.data_ptr() if t is not None else None
 
 
+def _m_dev_ptr(who, M_dev):
+    """the device row count's address (None without one)"""
+    if M_dev is None:
+        return None
+    if M_dev.dtype != torch.int64 or not M_dev.is_cuda:
+        raise RuntimeError(f"{who}: M_dev must be a device int64 scalar")
+    return M_dev.data_ptr()
+
+
+def _check_rows(who, res32=None, out32=None, res16=None, gate16=None):
+    """dtype and layout of the epilogue's row tensors"""
+    for t, nm in ((res32, "res32"), (out32, "out32")):
+        if t is not None and (t.dtype != torch.float32 or t.stride(1) != 1):
+            raise RuntimeError(f"{who}: {nm} must be fp32 with contiguous rows")
+    for t, nm in ((res16, "res16"), (gate16, "gate16")):
+        if t is not None and (t.dtype != torch.float16 or not t.is_contiguous() or t.shape[-1] != WIDTH):
+            raise RuntimeError(f"{who}: {nm} must be contiguous fp16 [*, 384]")
+
+
+def _gemm_args(who, W, K, bias, A=None, a_idx=None, M=0, flags=0, M_dev=None, res32=None, res16=None, res16_idx=None,
+               gate16=None, ln=None, heads=None, head_out=None, out32=None, out16=None):
+    """One GEMM's RowGemmArgs from tensors (`who` prefixes the messages).  A: the
+    rows the GEMM reads (with a_idx, M and the zero row; None for a later GEMM of
+    a chain); res32 .. out16: the epilogue's inputs and outputs, checked by
+    _check_rows; index tensors must be int64 already."""
+    _check_rows(who, res32, out32, res16, gate16)
+    a = RowGemmArgs()
+    if A is not None:
+        a.A, a.lda, a.a_idx, a.a_rows = _p(A), A.stride(0), _p(a_idx), A.shape[0]
+        a.zero_row = _p(zero_row(A.device, K))
+    a.W, a.K, a.N, a.bias = _p(W), K, WIDTH, _p(bias)
+    a.M, a.flags, a.M_dev = M, int(flags), _m_dev_ptr(who, M_dev)
+    a.res32, a.ldr = _p(res32), (res32.stride(0) if res32 is not None else 0)
+    a.res16, a.res16_idx, a.gate16 = _p(res16), _p(res16_idx), _p(gate16)
+    if ln is not None:
+        a.ln_g, a.ln_b, a.ln_eps = _p(ln[0]), _p(ln[1]), float(ln[2])
+    if heads is not None:
+        a.head_w, a.head_b, a.head_out = _p(heads[0]), _p(heads[1]), _p(head_out)
+    a.out32, a.ldo32 = _p(out32), (out32.stride(0) if out32 is not None else 0)
+    a.out16, a.ldo16 = _p(out16), (out16.stride(0) if out16 is not None else 0)
+    return a
+
+
 def rowgemm(A, W16, b16, flags=0, a_idx=None, M=None, res32=None, res16=None, res16_idx=None, gate16=None, ln=None,
             heads=None, out32=None, out16=None, want32=False, want16=True, M_dev=None):
     """Y = epilogue(A W^T + b) over 384-wide rows (see include/dpvo_hot.h).
@@ -413,29 +431,8 @@ def rowgemm(A, W16, b16, flags=0, a_idx=None, M=None, res32=None, res16=None, re
     head_out = H.empty(M, 4, dtype=torch.float16, device=dev) if heads is not None else None
     if res16_idx is not None:
         res16_idx = H.idx64(res16_idx)
-    a = RowGemmArgs()
-    a.A, a.lda, a.a_idx, a.a_rows = _p(A), A.stride(0), _p(a_idx), A.shape[0]
-    a.W, a.K, a.N, a.bias, a.zero_row = _p(W16), Kp, WIDTH, _p(b16), _p(zero_row(dev, Kp))
-    a.M = M
-    a.res32, a.ldr = _p(res32), (res32.stride(0) if res32 is not None else 0)
-    a.res16, a.res16_idx, a.gate16 = _p(res16), _p(res16_idx), _p(gate16)
-    if ln is not None:
-        a.ln_g, a.ln_b, a.ln_eps = _p(ln[0]), _p(ln[1]), float(ln[2])
-    if heads is not None:
-        a.head_w, a.head_b, a.head_out = _p(heads[0]), _p(heads[1]), _p(head_out)
-    a.out32, a.ldo32 = _p(out32), (out32.stride(0) if out32 is not None else 0)
-    a.out16, a.ldo16 = _p(out16), (out16.stride(0) if out16 is not None else 0)
-    a.flags = int(flags)
-    if M_dev is not None:
-        if M_dev.dtype != torch.int64 or not M_dev.is_cuda:
-            raise RuntimeError("rowgemm: M_dev must be a device int64 scalar")
-        a.M_dev = M_dev.data_ptr()
-    for t, nm in ((res32, "res32"), (out32, "out32")):
-        if t is not None and (t.dtype != torch.float32 or t.stride(1) != 1):
-            raise RuntimeError(f"rowgemm: {nm} must be fp32 with contiguous rows")
-    for t, nm in ((res16, "res16"), (gate16, "gate16")):
-        if t is not None and (t.dtype != torch.float16 or not t.is_contiguous() or t.shape[-1] != WIDTH):
-            raise RuntimeError(f"rowgemm: {nm} must be contiguous fp16 [*, 384]")
+    a = _gemm_args("rowgemm", W16, Kp, b16, A=A, a_idx=a_idx, M=M, flags=flags, M_dev=M_dev, res32=res32, res16=res16,
+                   res16_idx=res16_idx, gate16=gate16, ln=ln, heads=heads, head_out=head_out, out32=out32, out16=out16)
     H.check(H.lib().dpvo_rowgemm(_ct.byref(a), H.stream_of(A)))
     return out32, out16, head_out
 
@@ -459,17 +456,8 @@ def rowgemm_pair(A, Wa, ba, Wb, bb, M_dev=None):
     args = []
     for W, b in ((Wa, ba), (Wb, bb)):
         o = H.empty(M, WIDTH, dtype=torch.float16, device=dev)
-        a = RowGemmArgs()
-        a.A, a.lda, a.a_idx, a.a_rows = _p(A), A.stride(0), None, M
-        a.W, a.K, a.N, a.bias, a.zero_row = _p(W), Kp, WIDTH, _p(b), _p(zero_row(dev, Kp))
-        a.M, a.flags = M, WKB if kb else 0
-        a.out16, a.ldo16 = _p(o), o.stride(0)
-        if M_dev is not None:
-            if M_dev.dtype != torch.int64 or not M_dev.is_cuda:
-                raise RuntimeError("rowgemm_pair: M_dev must be a device int64 scalar")
-            a.M_dev = M_dev.data_ptr()
         outs.append(o)
-        args.append(a)
+        args.append(_gemm_args("rowgemm_pair", W, Kp, b, A=A, M=M, flags=WKB if kb else 0, M_dev=M_dev, out16=o))
     H.check(H.lib().dpvo_rowgemm_pair(_ct.byref(args[0]), _ct.byref(args[1]), H.stream_of(A)))
     return outs[0], outs[1]
 
@@ -493,12 +481,9 @@ def rowgemm_pair_pre(a32, b16, b_idx, Wa, ba, Wb, bb, b_rows=None):
     outs, args = [], []
     for W, b in ((Wa, ba), (Wb, bb)):
         o = H.empty(M, WIDTH, dtype=torch.float16, device=dev)
-        a = RowGemmArgs()
-        z = _p(zero_row(dev, Kp))
-        a.A, a.lda, a.a_idx, a.a_rows = z, Kp, None, M   # (A unused: the rows are pre's)
-        a.W, a.K, a.N, a.bias, a.zero_row = _p(W), Kp, WIDTH, _p(b), z
-        a.M, a.flags = M, WKB
-        a.out16, a.ldo16 = _p(o), o.stride(0)
+        a = _gemm_args("rowgemm_pair_pre", W, Kp, b, M=M, flags=WKB, out16=o)
+        a.A = a.zero_row = _p(zero_row(dev, Kp))   # (A unused: the rows are pre's)
+        a.lda, a.a_rows = Kp, M
         outs.append(o)
         args.append(a)
     pre = RowAddArgs()

@@ -256,6 +256,11 @@ __global__ __launch_bounds__(256) void bd_prep_kernel(BdParams p)
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < p.E; q += stride) {
         const int64_t e = p.perm[q];
+        // every edge's patch index, not only each group's first: the group-by
+        // keeps the low bits of kk, so an index past the end can share a group
+        // with a valid patch
+        const int64_t k = p.kk[e];
+        if (k < 0 || k >= p.num_patches) atomicExch(p.status, -1);
         p.erec[2 * q] = bd_f4v{__int_as_float((int)p.ii[e]), __int_as_float((int)p.jj[e]), p.target[2 * e],
                                p.target[2 * e + 1]};
         p.erec[2 * q + 1] = bd_f4v{p.weight[2 * e], p.weight[2 * e + 1], 0.f, 0.f};

@@ -301,6 +301,28 @@ int dpvo_sim3_ransac(const double* src, const double* dst, int64_t N, const int*
 int dpvo_sim3_umeyama(const double* src, const double* dst, int64_t N, const unsigned char* mask, double* out_sim3,
                       int* out_info, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Loop-closure retrieval (netvlad_retrieval.py:89-104, query_online, for Q
+ * queries at once; csrc/retrieval.hip).  db [N] rows of D fp32 descriptors,
+ * row stride ld floats; query q is row n = query_rows[q] (int64 [Q], device),
+ * its candidates the rows r in [0, n - skip_window).  out_val / out_idx
+ * [Q][top_k] fp32 / int64: the top_k largest fp32 dot products <db[r], db[n]>
+ * in non-increasing order with their rows, bitwise-equal scores by ascending
+ * row; the unused tail (fewer candidates than top_k, none when
+ * n <= skip_window) holds (-inf, -1).  out_scores (may be NULL) [Q][N]: every
+ * candidate's score, -inf elsewhere.  Rows at or beyond n - skip_window reach
+ * no output (they may hold NaN).  fp32 FMA accumulation, lane l over the
+ * elements 4 l + 256 i .. + 3 in ascending i, then one fixed wave reduction:
+ * the bits of a score depend on its two rows and D alone -- not on Q, the
+ * query's place in the batch, N, or what the workspace held.  A query row
+ * outside [0, N) gets an all-tail result and reads nothing out of bounds (the
+ * Python shim refuses it on the host).  D % 4 == 0, ld >= D, ld % 4 == 0, db
+ * 16-byte aligned, 1 <= top_k <= 32, 1 <= N <= 2^24, 1 <= Q <= 2^16,
+ * skip_window >= 0.  No host read. */
+size_t dpvo_retrieval_workspace_bytes(int64_t Q, int64_t N, int top_k);
+int dpvo_retrieval_query(const float* db, int64_t ld, int64_t N, int D, const int64_t* query_rows, int64_t Q,
+                         int64_t skip_window, int top_k, float* out_val, int64_t* out_idx, float* out_scores,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * lietorch -- replaces lietorch_backends (reference lietorch.cpp:286-316)
  * group: 1 = SO3, 3 = SE3 (dispatch.h:16-31); dtype F32 or F64.

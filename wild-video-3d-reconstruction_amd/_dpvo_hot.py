@@ -66,6 +66,8 @@ _SIGNATURES = {
     "dpvo_sim3_workspace_bytes": (_sz, [_i64, _i64]),
     "dpvo_sim3_ransac": (_ip, [_vp, _vp, _i64, _vp, _i64, _dp, _ip, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dpvo_sim3_umeyama": (_ip, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dpvo_retrieval_workspace_bytes": (_sz, [_i64, _i64, _ip]),
+    "dpvo_retrieval_query": (_ip, [_vp, _i64, _i64, _ip, _vp, _i64, _i64, _ip, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dpvo_neighbors_workspace_bytes": (_sz, [_i64]),
     "dpvo_neighbors": (_ip, [_vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "dpvo_lie_forward": (_ip, [_ip, _ip, _ip, _vp, _vp, _vp, _i64, _vp]),

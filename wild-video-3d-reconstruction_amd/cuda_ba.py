@@ -360,3 +360,51 @@ def umeyama(src, dst, mask=None):
     H.check(H.lib().dpvo_sim3_umeyama(H.ptr(src), H.ptr(dst), N, H.ptr(mask), H.ptr(sim3), H.ptr(info), H.ptr(ws),
                                       nbytes, H.stream_of(src)))
     return sim3, info
+
+
+# ---------------------------------------------------------------------------
+# Loop-closure retrieval (the reference's query_online, netvlad_retrieval.py:
+# 89-104, for Q queries in one call; csrc/retrieval.hip).  Scores are fp32
+# dot products whose bits depend on the two rows alone: one query at a time
+# and a batch give the same bits.
+# ---------------------------------------------------------------------------
+def retrieval_query(db, query_rows, skip_window, top_k=1, return_scores=False):
+    """db [N, D] fp32 on the device (rows may be strided: db.stride(0) is the
+    leading dimension); query_rows: Q row indices, as host integers (a
+    sequence or a CPU tensor: checked against [0, N) with no device read) or
+    as a device tensor (checked with one device->host copy).  Query n's
+    candidates are the rows [0, n - skip_window).
+
+    -> (val [Q, top_k] fp32, idx [Q, top_k] int64[, scores [Q, N] fp32]), on
+    the device: the top_k largest <db[r], db[n]> in non-increasing order, ties
+    by ascending row, the unused tail (-inf, -1); scores holds every
+    candidate's score and -inf elsewhere."""
+    H.on_gpu(db)
+    if db.dtype != torch.float32:
+        raise RuntimeError(f"retrieval_query: db must be float32, got {db.dtype}")
+    if db.dim() != 2 or db.shape[0] < 1 or db.shape[1] < 1 or db.stride(1) != 1:
+        raise RuntimeError("retrieval_query: db must be [N, D] with unit stride along D")
+    N, D = db.shape
+    ld = db.stride(0) if N > 1 else max(db.stride(0), D)
+    dev = db.device
+    if torch.is_tensor(query_rows):
+        if torch.is_floating_point(query_rows) or query_rows.dim() != 1:
+            raise RuntimeError("retrieval_query: query_rows must be a 1-D integer tensor or a sequence of integers")
+        rows = [int(v) for v in query_rows.tolist()]
+    else:
+        rows = [int(v) for v in query_rows]
+    Q = len(rows)
+    bad = [n for n in rows if n < 0 or n >= N]
+    if bad:
+        raise RuntimeError(f"retrieval_query: query row {bad[0]} outside [0, {N})")
+    top_k, skip_window = int(top_k), int(skip_window)
+    val = H.empty(Q, max(top_k, 0), dtype=torch.float32, device=dev)
+    idx = H.empty(Q, max(top_k, 0), dtype=torch.int64, device=dev)
+    scores = H.empty(Q, N, dtype=torch.float32, device=dev) if return_scores else None
+    if Q > 0:
+        qr = torch.tensor(rows, dtype=torch.int64).to(dev)
+        nbytes = H.lib().dpvo_retrieval_workspace_bytes(Q, N, top_k)
+        ws = H.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+        H.check(H.lib().dpvo_retrieval_query(H.ptr(db), ld, N, D, H.ptr(qr), Q, skip_window, top_k, H.ptr(val),
+                                             H.ptr(idx), H.ptr(scores), H.ptr(ws), nbytes, H.stream_of(db)))
+    return (val, idx, scores) if return_scores else (val, idx)

@@ -3,8 +3,10 @@
 Public API kept: DPVO(cfg, network, ht, wd, ...), __call__(tstamp, image,
 depth, mask, intrinsics), update(), keyframe(), terminate(),
 terminate_keyframe(), get_pts_clr_intri(), global_bundle_adjustment().
-Visualisation (rerun/viewer), inlier-ratio records, SuperPoint and loop
-closure are out of scope.
+Visualisation (rerun/viewer), inlier-ratio records and SuperPoint are out of
+scope.  Loop closure (cfg.loop_enabled) runs natively from
+retrieval to the pose graph; its keypoint detector and matcher are the
+caller's (loop_frontend=).
 
 MI355X-specific choices (all behind the same API):
   * the fmap rings are stored channel-last ([pmem, H, W, C], exposed through
@@ -40,13 +42,22 @@ def _ring(pmem, C, h, w, channel_last, **kw):
 
 class DPVO:
     def __init__(self, cfg, network, ht=480, wd=640, viz=False, path="", nvlad_db=None, rerun=False,
-                 device="cuda"):
+                 device="cuda", loop_frontend=None):
+        """cfg.loop_enabled builds the long-term loop closer (dpvo.py:101-102):
+        retrieval over nvlad_db, loop detection, the image cache and the
+        Sim(3) back end are native; keypoint detection and matching come from
+        loop_frontend (loop_closure.LongTermLoopClosure).  With loop closure on,
+        cfg.DEFER_KEYFRAME loses its overlap: every __call__ applies the
+        keyframe decision at its end, before the loop closer compares
+        keyframe indices."""
         if viz or rerun:
             raise NotImplementedError("visualisation is out of scope for the MI355X hot-path build")
-        if getattr(cfg, "loop_enabled", False):
-            # the reference builds a retrieval + DISK/LightGlue + Sim(3) PGO loop
-            # closer here (dpvo.py:101-102); it needs remote weights and is out of scope
-            raise NotImplementedError("cfg.loop_enabled: loop closure is out of scope for the MI355X hot-path build")
+        self.long_term_lc = None
+        if getattr(cfg, "loop_enabled", False) and (nvlad_db is None or loop_frontend is None):
+            # the reference builds DISK + LightGlue here from remote weights; this
+            # build takes them from the caller
+            raise NotImplementedError("cfg.loop_enabled: loop closure needs both nvlad_db= (the precomputed "
+                                      "descriptors) and loop_frontend= (keypoint tracks and matches)")
         self.cfg = cfg
         self.device = torch.device(device)
         self.load_weights(network)
@@ -86,6 +97,9 @@ class DPVO:
         self._ba_fail = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._ugraph = None
         self._identity = SE3.Identity(1, device=self.device)
+        if getattr(cfg, "loop_enabled", False):
+            from .loop_closure import LongTermLoopClosure
+            self.long_term_lc = LongTermLoopClosure(cfg, self.pg, nvlad_db, loop_frontend, ht, wd)
 
     # ------------------------------------------------------------------ state views
     @property
@@ -168,6 +182,8 @@ class DPVO:
     def terminate(self):
         self.flush_keyframe()
         self.check_ba()
+        if self.long_term_lc is not None:
+            self.long_term_lc.terminate(self.n)
         if self.enable_global_ba:
             self.global_bundle_adjustment()
         self.traj = {self.pg.tstamps_[i].item(): self.pg.poses_[i] for i in range(self.n)}
@@ -177,6 +193,8 @@ class DPVO:
 
     def terminate_keyframe(self):
         self.flush_keyframe()
+        if self.long_term_lc is not None:
+            self.long_term_lc.terminate(self.n)
         self.traj = {self.pg.tstamps_[i].item(): self.pg.poses_[i] for i in range(self.n)}
         poses = stack([SE3(self.pg.poses_[i]) for i in range(self.n)], dim=0).inv().data.cpu().numpy()
         return poses, torch.as_tensor([self.pg.tstamps_[i] for i in range(self.n)], dtype=torch.float64).numpy()
@@ -199,8 +217,9 @@ class DPVO:
         below max(loop_ii) + 1 are corrected in place (PatchGraph.close_loop).
         update() reads poses_ / patches_ afresh on every call (also when
         graph-captured: the buffers are written in place), so nothing else is
-        cached.  Retrieval and matching are the caller's: cfg.loop_enabled
-        still raises."""
+        cached.  This entry is for a caller with its own retrieval and
+        matching; cfg.loop_enabled drives the same back end from the native
+        retrieval."""
         self.flush_keyframe()
         self.check_ba()
         return self.pg.close_loop(i, j, far_rel_pose)
@@ -637,7 +656,9 @@ class DPVO:
         __call__, update(), update_graphed(), terminate(), terminate_keyframe(),
         global_bundle_adjustment(), get_pts_clr_intri(), get_pose() or
         flush_keyframe().  The plain state views (n, m, poses, patches, pg.*)
-        do NOT apply it: call flush_keyframe() before reading them."""
+        do NOT apply it: call flush_keyframe() before reading them.  With
+        cfg.loop_enabled the same __call__ applies it at its end (the loop
+        closer compares keyframe indices), so nothing is overlapped."""
         self.flush_keyframe()
         pend = self._keyframe_begin()
         if getattr(self.cfg, "DEFER_KEYFRAME", False):
@@ -702,6 +723,8 @@ class DPVO:
             self.n -= 1
             self.pg.m -= self.M
             self.keyframes_dropped = getattr(self, "keyframes_dropped", 0) + 1
+            if self.long_term_lc is not None:
+                self.long_term_lc.keyframe(k)
             # frame k's edges and the retired ones in one compaction (stable,
             # so the same order as the reference's two)
             self.remove_factors(pd["rm_d"], store=pd["old_d"], counts=(E - n_rm_d, n_old_d))
@@ -849,6 +872,8 @@ class DPVO:
         self.fmap1_[:, slot] = fmap[0]   # avg_pool2d(fmap[0], 1, 1) (dpvo.py:840) is the identity
         self.fmap2_[:, slot] = F.avg_pool2d(fmap[0], 4, 4)
         self.image_buffer_[n % self.mem] = image
+        if self.long_term_lc is not None:
+            self.long_term_lc(image, n, self.counter)
         self.counter += 1
         if n > 0 and not self.is_initialized:
             if self.motion_probe() < 2.0:
@@ -872,3 +897,8 @@ class DPVO:
         elif self.is_initialized:
             self.update()
             self.keyframe()
+        if self.long_term_lc is not None:
+            # the (deferred) keyframe decision first: the loop closer compares keyframe indices
+            self.flush_keyframe()
+            self.long_term_lc.attempt_loop_closure(self.n)
+            self.long_term_lc.lc_callback()

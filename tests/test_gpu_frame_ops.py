@@ -65,6 +65,27 @@ def test_append_edges_equals_the_reference_construction(n, M, r, E):
         assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize("r", [1, 13])
+@pytest.mark.parametrize("M", [1, 4])
+def test_append_edges_count_equals_the_growth_of_the_edge_list(M, r):
+    """dpvo_append_edges_count against what the kernel appends (both take the
+    ranges from one place) and against the reference construction's length,
+    where n - r changes sign and the forward range is empty (n = 1: no earlier
+    frame)."""
+    import _dpvo_hot
+    import update_ops
+    ix = torch.arange(32, device="cuda").repeat_interleave(M)
+    for n in sorted({1, 2, r, r + 1}):
+        count = _dpvo_hot.lib().dpvo_append_edges_count(n, M, r)
+        for E in (0, 3):
+            old = torch.arange(E, device="cuda")
+            got = update_ops.append_edges(old, old, old, ix, n, M, r)
+            want = reference_append(old, old, old, ix, n, M, r)
+            assert count == len(want[0]) - E, (n, M, r, count)
+            for a, b in zip(got, want):
+                assert torch.equal(a, b), (n, M, r, E)
+
+
 def test_append_edges_errors():
     import update_ops
     x = torch.zeros(3, dtype=torch.int64, device="cuda")

@@ -1,7 +1,7 @@
-"""Native update-operator glue (csrc/updateop.hip) against the oracle:
-SoftAgg's grouped softmax-sum (torch_scatter scatter_softmax + scatter_sum,
-reference dpvo/blocks.py:40-48) and the masked neighbour gather
-(dpvo/net.py:82-85)."""
+"""Native update-operator glue against the oracle: SoftAgg's grouped
+softmax-sum (torch_scatter scatter_softmax + scatter_sum, reference
+dpvo/blocks.py:40-48) and the masked neighbour gather (dpvo/net.py:82-85) of
+csrc/updateop.hip, and the group-by of csrc/groupby.hip."""
 import numpy as np
 import pytest
 import torch

@@ -6,8 +6,8 @@ scatter_sum in SoftAgg, :42-43), dpvo/net.py:8-9, dpvo/ba.py:2 (scatter_sum,
 no ROCm wheel of torch-scatter; this module, on the path next to the
 ``cuda_corr`` / ``cuda_ba`` / ``lietorch_backends`` shims, lets the
 reference's Python import and run unchanged.  Every reduction is one
-``dpvo_scatter_csr`` launch over the device group-by of the index
-(csrc/updateop.hip): deterministic (members summed in ascending order), no
+``dpvo_scatter_csr`` launch (csrc/scatter.hip) over the device group-by of the
+index (csrc/groupby.hip): deterministic (members summed in ascending order), no
 atomics.  Like the other shims it refuses CPU tensors.
 
 Supported: a 1-D index along ``dim`` (the form every reference call uses), or

@@ -1,4 +1,6 @@
-"""Native glue of the learned update operator (csrc/updateop.hip).
+"""Native glue of the learned update operator: SoftAgg, the row gather and the
+edge targets (csrc/updateop.hip) and the tracker's edge bookkeeping -- group-by,
+window keys, CSR neighbours, edge append (csrc/groupby.hip).
 
 Replaces torch_scatter 2.1.2's ``scatter_softmax`` + ``scatter_sum`` in
 SoftAgg (reference dpvo/blocks.py:40-48) and the masked neighbour gather of

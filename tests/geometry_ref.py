@@ -1,8 +1,9 @@
-"""fp64 restatement of the projective and keyframe kernels (csrc/geometry.hip)
-with the error companions their tests are held to.  Plain numpy, no GPU, no
-oracle: it follows dpvo/projective_ops.py and the header comments of
-include/dpvo_hot.h, with rotation matrices instead of the kernels' quaternion
-products, so it shares no statement order with the code under test.
+"""fp64 restatement of the projective kernels (csrc/geometry.hip, the keyframe
+distance matrix among them) with the error companions their tests are held
+to.  Plain numpy, no GPU, no oracle: it follows dpvo/projective_ops.py and the
+header comments of include/dpvo_hot.h, with rotation matrices instead of the
+kernels' quaternion products, so it shares no statement order with the code
+under test.
 
 With unit quaternions (the inputs are normalised here, as on every load there):
 

@@ -1,9 +1,10 @@
-"""Kernel-level tests of csrc/geometry.hip through the C ABI: the projective
-kernels against the fp64 restatement of tests/geometry_ref.py, each float
-output within k S of it (k counted from the code, S the output's own magnitude
-sum -- see that module), and the keyframe bookkeeping kernels (masks, frame
-shift, edge compaction) bit-exact against torch / numpy.  Every output is a
-view between guard bytes of a poisoned buffer; the guards must survive."""
+"""Kernel-level tests of csrc/geometry.hip and csrc/keyframe.hip through the C
+ABI: the projective kernels against the fp64 restatement of
+tests/geometry_ref.py, each float output within k S of it (k counted from the
+code, S the output's own magnitude sum -- see that module), and the keyframe
+bookkeeping kernels of keyframe.hip (masks, frame shift, edge compaction)
+bit-exact against torch / numpy.  Every output is a view between guard bytes
+of a poisoned buffer; the guards must survive."""
 import ctypes
 import functools
 

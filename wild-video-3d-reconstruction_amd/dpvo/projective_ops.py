@@ -5,7 +5,10 @@ semantics.  The inference forms (batch 1, no autograd, no Jacobians) run as
 one fused HIP kernel each (csrc/geometry.hip): the reference composes ~30
 launches and materialises E*P*P broadcast pose copies.  The differentiable /
 Jacobian forms compose the lietorch operators exactly as the reference does.
+The keyframe bookkeeping shims (masks, frame shift) call csrc/keyframe.hip.
 """
+import ctypes
+
 import torch
 
 import _dpvo_hot as H
@@ -149,7 +152,6 @@ def frame_shift(buffers, k, n):
         bases.append(t.data_ptr())
         sizes.append(t.stride(d) * t.element_size())
         rings.append(int(ring or 0))
-    import ctypes
     ns = len(bases)
     H.check(H.lib().dpvo_frame_shift((ctypes.c_void_p * ns)(*bases), (ctypes.c_int64 * ns)(*sizes),
                                      (ctypes.c_int64 * ns)(*rings), ns, int(k), int(n), H.stream_of(buffers[0][0])))

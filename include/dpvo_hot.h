@@ -721,6 +721,32 @@ int dpvo_patch_gather(const void* fmap, const int64_t* fmap_strides, int h, int 
                       const uint8_t* image, int H, int W, const float* lut, const int64_t* x, const int64_t* y,
                       int64_t M, float* gmap, float* imap, float* patches, float* clr, void* stream);
 
+/* The Patchifier's gradient-biased centre choice (net.py:103-109,129-134), one
+ * launch: of the C candidates (cand_x[c], cand_y[c]) on the stride-4 map, the M
+ * with the largest image gradient.  score[c] = the mean over the 4x4 block at
+ * (4 y, 4 x) of sqrt(dx^2 + dy^2), dx = gray[r][c+1] - gray[r][c], dy =
+ * gray[r+1][c] - gray[r][c], gray = R + G + B of the uint8 frame [3][H][W] (an
+ * exact integer; 16 correctly rounded square roots added in fp32 in row-major
+ * order, times 1/16); 0 where the block lies outside the pooled
+ * [(H-1)/4][(W-1)/4] map.  The candidates are ordered by (score, index)
+ * ascending -- a stable argsort -- and out[m] is the one of rank C - M + m;
+ * duplicates stay duplicates.  scores: float [C] or NULL.  C <= 8192, M <= C,
+ * H, W >= 8. */
+int dpvo_select_gradient(const uint8_t* image, int H, int W, const int64_t* cand_x, const int64_t* cand_y,
+                         int64_t C, int64_t M, int64_t* out_x, int64_t* out_y, float* scores, void* stream);
+
+/* The Patchifier's masked centre choice (net.py:141-144), two launches whatever
+ * the mask holds.  Cell (cy, cx) of the h x w stride-4 map is valid iff some
+ * mask[r][c] != 0 (uint8 [H][W]) has r / 4 == cy and c / 4 == cx, and cx < w - 1
+ * and cy < h - 1.  The valid cells are ordered by (keys[cy w + cx], cy w + cx)
+ * ascending (keys int32 [h w], non-negative: drawn i.i.d. by the caller they
+ * make out a uniform M-subset in uniform order); out[m] is the m-th of them,
+ * count[0] = K their number.  For K < M, out[m] = out[m mod K]; for K == 0
+ * every output is (1, 1).  M <= 4096; workspace: 16-byte aligned. */
+size_t dpvo_select_mask_workspace_bytes(int h, int w);
+int dpvo_select_mask(const uint8_t* mask, int H, int W, int h, int w, const int* keys, int64_t M, int64_t* out_x,
+                     int64_t* out_y, int* count, void* workspace, void* stream);
+
 /* keyframe() (dpvo.py:605-658): both outcomes' edge state before the decision,
  * and the decision's one host read.  For edge e, k the candidate frame:
  *   masks[0][e] = ix[kk] < n - RW (keep: edges retired, :654-658)

@@ -1,7 +1,8 @@
 """Frame-ingest timing (row f1): Patchifier on one 512x384 frame under fp16
 autocast -- eager, graph-replayed, and the encoders in channels-last memory
 format -- with HIP events.  Run under rocprofv3 --kernel-trace for the
-per-kernel split."""
+per-kernel split.  `--select`: the ingest by centre choice instead (uniform,
+gradient_bias, mask=; see select_modes)."""
 import os
 import sys
 import time
@@ -22,7 +23,43 @@ def timed(fn, n=50):
     return (time.perf_counter() - t0) / n * 1e3
 
 
+def select_modes(repeats=3, n=100):
+    """`--select`: the ingest by centre choice -- uniform, gradient_bias and
+    mask= (half of the frame set) -- on one 512x384 frame at M = 96 and 384,
+    eager and graph-replayed, with the native selection (csrc/select.hip) and
+    with Patchifier.NATIVE_SELECT = False (the torch branches; the only ones a
+    tree without the switch has).  Each row: (min, max) ms per frame over
+    `repeats` windows of n frames, the variants of a mode interleaved."""
+    import json
+    from dpvo.net import Patchifier, VONet
+    torch.manual_seed(0)
+    pf = VONet().cuda().eval().patchify
+    img8 = torch.randint(0, 255, (3, 384, 512), device="cuda", dtype=torch.uint8)
+    mask = torch.zeros(384, 512, dtype=torch.bool, device="cuda")
+    mask[:, :256] = True
+    variants = [("native", True), ("torch", False)] if hasattr(Patchifier, "NATIVE_SELECT") else [("torch", None)]
+    res = {}
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+        for M in (96, 384):
+            for mode, kw in (("uniform", {}), ("gradient", dict(gradient_bias=True)), ("mask", dict(mask=mask))):
+                rows = {}
+                for _ in range(repeats):
+                    for tag, native in (variants if mode != "uniform" else variants[:1]):
+                        for graphed in (False, True):
+                            if native is not None:
+                                Patchifier.NATIVE_SELECT = native
+                            pf.graphed = graphed
+                            name = f"{mode}_M{M}_{tag if mode != 'uniform' else 'native'}_{'graph' if graphed else 'eager'}_ms"
+                            rows.setdefault(name, []).append(timed(lambda: pf(img8, M, return_color=True, **kw), n))
+                res.update({k: (round(min(v), 3), round(max(v), 3)) for k, v in rows.items()})
+    if hasattr(Patchifier, "NATIVE_SELECT"):
+        Patchifier.NATIVE_SELECT = True
+    print(json.dumps(res), flush=True)
+
+
 def main():
+    if "--select" in sys.argv[1:]:
+        return select_modes()
     from dpvo.net import VONet
     torch.manual_seed(0)
     net = VONet().cuda().eval()

@@ -119,6 +119,9 @@ _SIGNATURES = {
                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dpvo_patch_gather": (_ip, [_vp, _vp, _ip, _ip, _vp, _ip, _vp, _ip, _ip, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                 _vp, _vp]),
+    "dpvo_select_gradient": (_ip, [_vp, _ip, _ip, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "dpvo_select_mask_workspace_bytes": (_sz, [_ip, _ip]),
+    "dpvo_select_mask": (_ip, [_vp, _ip, _ip, _ip, _ip, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTED = tuple(_SIGNATURES)
 

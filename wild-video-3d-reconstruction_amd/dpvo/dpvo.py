@@ -32,6 +32,7 @@ from .utils import Timer, flatmeshgrid
 
 
 CORR_DIM, CORR_ROW = 882, 896  # 2 levels x 7 x 7 x 3 x 3 features; padded row
+_NO_MASK = float(2 ** 31 - 1)  # the valid-cell word while no masked frame has been seen
 
 
 def _ring(pmem, C, h, w, channel_last, **kw):
@@ -95,6 +96,9 @@ class DPVO:
         # first failure since the last host check -- update() never syncs
         self._ba_status = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._ba_fail = torch.zeros(1, dtype=torch.int32, device=self.device)
+        # the fewest valid mask cells of a natively masked frame since the last
+        # host check (Patchifier.last_mask_cells); None until a mask is seen
+        self._mask_cells = None
         self._ugraph = None
         self._identity = SE3.Identity(1, device=self.device)
         if getattr(cfg, "loop_enabled", False):
@@ -608,9 +612,21 @@ class DPVO:
         the last check failed; status: that word already read by the caller."""
         if status is None:
             status = int(self._ba_fail.item())
+            if self._mask_cells is not None:
+                cells = int(self._mask_cells.item())
+                self._mask_cells.fill_(_NO_MASK)
+                self.check_mask_cells(cells)
         if status:
             self._ba_fail.zero_()
             cuda_ba.raise_for_status(status)
+
+    def check_mask_cells(self, cells):
+        """a masked frame needs PATCHES_PER_FRAME valid cells (the reference
+        fails at its view(n, patches_per_image), net.py:144-145); cells: the
+        fewest of the frames since the last check, as read by the caller."""
+        if cells < self.M:
+            raise RuntimeError(f"the mask left {int(cells)} valid cells on a frame, fewer than "
+                               f"PATCHES_PER_FRAME = {self.M}")
 
     def update_graphed(self, t0=None):
         """update(), replayed from a HIP graph while the patch graph is
@@ -690,8 +706,13 @@ class DPVO:
                                                  mm, self._ba_fail, self.pg.poses_[k])
         host = getattr(self, "_kf_host", None)
         if host is None:
-            host = self._kf_host = torch.empty(7, dtype=torch.float64, pin_memory=True)
-        host.copy_(vals, non_blocking=True)
+            host = self._kf_host = torch.empty(8, dtype=torch.float64, pin_memory=True)
+        host[:7].copy_(vals, non_blocking=True)
+        # the masked frames' fewest valid cells ride on the same read
+        host[7] = _NO_MASK
+        if self._mask_cells is not None:
+            host[7:].copy_(self._mask_cells, non_blocking=True)
+            self._mask_cells.fill_(_NO_MASK)
         ev = torch.cuda.Event()
         ev.record()
         return dict(k=k, E=self.pg.kk.numel(), old_keep=masks[0], old_d=masks[1], rm_d=masks[2], idx_d=idx_d,
@@ -701,6 +722,7 @@ class DPVO:
         pd["event"].synchronize()
         vals = self._kf_host.tolist()
         k, E = pd["k"], pd["E"]
+        self.check_mask_cells(vals[7])
         self.check_ba(int(vals[2]))
         n_old_keep, n_old_d, n_rm_d = (int(v) for v in vals[4:7])
         m = vals[0] + vals[1]
@@ -832,6 +854,11 @@ class DPVO:
             fmap, gmap, imap, patches, _, clr = self.network.patchify(
                 image, patches_per_image=self.cfg.PATCHES_PER_FRAME, gradient_bias=self.cfg.GRADIENT_BIAS,
                 return_color=True, mask=mask)
+        cells = self.network.patchify.last_mask_cells
+        if cells is not None:   # a natively masked frame: too few cells raise at the next host check
+            if self._mask_cells is None:
+                self._mask_cells = torch.full((1,), _NO_MASK, dtype=torch.float64, device=self.device)
+            torch.minimum(self._mask_cells, cells, out=self._mask_cells)
         # the previous frame's deferred keyframe decision (cfg.DEFER_KEYFRAME),
         # its host read overlapping this frame's encoders
         self.flush_keyframe()

@@ -215,10 +215,16 @@ class Patchifier(nn.Module):
         self.graphed = True
         self._graph = self._graph_key = None
         self._native = None
+        # after a natively masked forward(): the number of valid mask cells, int32 [1] on the device
+        self.last_mask_cells = None
 
     # fp16-autocast inference runs both encoders on the HIP library
     # (encoder_ops / csrc/encoder.hip); False = the modules' torch forward
     NATIVE_ENCODERS = True
+    # beside them, gradient_bias and mask= choose their centres on the device
+    # (csrc/select.hip) and take the native / graphed ingest; False = the torch
+    # branches of forward()
+    NATIVE_SELECT = True
 
     def _native_encoders(self):
         if self._native is None:
@@ -243,13 +249,21 @@ class Patchifier(nn.Module):
         """image [3,H,W] uint8 -> fmap, gmap, imap, patches, index[, colours] (net.py:260-325)."""
         if sp_extractor is not None:
             raise NotImplementedError("SuperPoint keypoints are out of scope")
-        if (self.graphed and not gradient_bias and mask is None and disps is None and images.is_cuda and images.dim() == 3
-                and not torch.is_grad_enabled()):
-            return self._forward_graphed(images, patches_per_image, return_color)
+        self.last_mask_cells = None
         amp = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None
-        if (self._use_native(amp, images) and not gradient_bias and mask is None and disps is None and images.is_cuda and
-                images.dim() == 3):
-            x, y = self._draw_centres(images, patches_per_image)
+        # gradient_bias wins over the mask, as in the branches below
+        mode = "gradient" if gradient_bias else "mask" if mask is not None else "uniform"
+        frame_ok = disps is None and images.is_cuda and images.dim() == 3
+        # the two selections are native only beside the native encoders; every
+        # other input keeps the torch branch below
+        mode_ok = mode == "uniform" or (
+            self.NATIVE_SELECT and frame_ok and self._use_native(amp, images) and images.shape[0] == 3 and
+            (mode == "gradient" or (mask.is_cuda and tuple(mask.shape) == tuple(images.shape[-2:]))))
+        if self.graphed and mode_ok and frame_ok and not torch.is_grad_enabled():
+            return self._forward_graphed(images, patches_per_image, return_color, mode, mask)
+        if self._use_native(amp, images) and mode_ok and frame_ok:
+            rnd = self._draw(images, patches_per_image, mode, mask)
+            x, y = self._centres(images, patches_per_image, mode, rnd)
             fmap, gmap, imap, patches, clr = self._ingest(images, x, y, return_color, "native")
             index = torch.zeros(patches_per_image, dtype=torch.long, device=images.device)
             return (fmap, gmap, imap, patches, index) + ((clr,) if return_color else ())
@@ -320,47 +334,93 @@ class Patchifier(nn.Module):
         imap = inet(images) / 4.0
         return (fmap,) + self._gather(images, fmap, imap, x, y, None, return_color)
 
-    def _forward_graphed(self, image, M, return_color):
+    def _forward_graphed(self, image, M, return_color, mode="uniform", mask=None):
         """forward() with the ~300 encoder / patchify launches replayed from
-        one HIP graph.  The patch centres are drawn eagerly with the same
-        randint calls, in the same order, as the eager path (the encoders draw
-        no random numbers), so the results are identical to forward()'s; the
-        graph reads them from static buffers.  Outputs are returned as clones:
-        the next replay overwrites the graph's own."""
+        one HIP graph.  The random inputs of the centre choice (_draw) are
+        drawn eagerly with the same calls, in the same order, as the eager path
+        (the encoders draw no random numbers), so the results are identical to
+        forward()'s; the graph reads them from static buffers and, in the
+        gradient and mask modes, makes the choice itself (_centres).  Outputs
+        are returned as clones: the next replay overwrites the graph's own.
+        One graph is kept and the mode is part of its key: a stream that
+        alternates modes (masked and unmasked frames, say) pays two warm-up
+        ingests and a capture at every switch -- a known cost; a graph per
+        mode would remove it."""
         dev = image.device
-        x, y = self._draw_centres(image, M)
+        rnd = self._draw(image, M, mode, mask)
         amp = torch.is_autocast_enabled("cuda")
         # the captured kernels hold raw parameter / buffer addresses and the
         # autocast dtype: any re-placement (.to(), .half(), load_state_dict
         # with assign=True), in-place update or a different autocast dtype re-captures
         tensors = (tuple((t.data_ptr(), t._version) for t in self.parameters()) +
                    tuple(t.data_ptr() for t in self.buffers()))
+        # (a change of mode captures again: one graph is kept)
         key = (tuple(image.shape), image.dtype, M, bool(return_color), amp,
-               torch.get_autocast_dtype("cuda") if amp else None, dev, tensors)
+               torch.get_autocast_dtype("cuda") if amp else None, dev, tensors, mode)
         if self._graph_key != key:
-            self._capture(image, x, y, return_color, amp, key)
+            self._capture(image, rnd, return_color, amp, key)
         self._g_in[0].copy_(image)
-        self._g_in[1].copy_(x)
-        self._g_in[2].copy_(y)
+        for buf, r in zip(self._g_in[1], rnd):
+            buf.copy_(r)
         self._graph.replay()
         fmap, gmap, imap, patches, clr = (t.clone() if t is not None else None for t in self._g_out)
+        if mode == "mask":
+            self.last_mask_cells = self._g_cells.clone()
         index = torch.zeros(M, dtype=torch.long, device=dev)
         if return_color:
             return fmap, gmap, imap, patches, index, clr
         return fmap, gmap, imap, patches, index
 
     @staticmethod
-    def _draw_centres(image, M):
-        """the default centre draw of forward() (net.py:292-294), on the stride-4 map"""
+    def _map_size(image):
         H, W = image.shape[-2:]
-        h, w = ((H + 1) // 2 + 1) // 2, ((W + 1) // 2 + 1) // 2  # conv1 (s2) then layer2 (s2)
+        return ((H + 1) // 2 + 1) // 2, ((W + 1) // 2 + 1) // 2  # conv1 (s2) then layer2 (s2)
+
+    @classmethod
+    def _draw_centres(cls, image, M):
+        """the default centre draw of forward() (net.py:292-294), on the stride-4 map"""
+        h, w = cls._map_size(image)
         x = torch.randint(1, w - 1, size=[1, M], device=image.device)
         y = torch.randint(1, h - 1, size=[1, M], device=image.device)
         return x, y
 
-    def _capture(self, image, x, y, return_color, amp, key):
+    def _draw(self, image, M, mode, mask):
+        """the random inputs of one frame's centre choice -- everything that
+        differs from frame to frame besides the frame; fixed shapes.  uniform:
+        the centres themselves; gradient: the 3 M candidates, the same two
+        randint calls as the torch branch (net.py:127-128); mask: the mask as
+        bytes (nonzero = set, any dtype) and one random key per cell."""
+        if mode == "uniform":
+            return self._draw_centres(image, M)
+        if mode == "gradient":
+            return self._draw_centres(image, 3 * M)
+        h, w = self._map_size(image)
+        keys = torch.randint(0, 2 ** 31 - 1, (h * w,), dtype=torch.int32, device=image.device)
+        return mask.ne(0).to(torch.uint8), keys
+
+    def _centres(self, image, M, mode, rnd):
+        """the M patch centres from _draw's inputs: launches of fixed shape and
+        no host read (csrc/select.hip), so part of the captured graph.  The
+        mask mode leaves the number of valid cells, a device word, in
+        last_mask_cells: fewer than M means repeated centres, for the caller
+        to refuse (DPVO does, where the reference fails at its view())."""
+        if mode == "uniform":
+            return rnd
+        import encoder_ops
+        if mode == "gradient":
+            x, y = encoder_ops.select_gradient(image, rnd[0], rnd[1], M)
+        else:
+            x, y, self.last_mask_cells = encoder_ops.select_mask(rnd[0], rnd[1], M, *self._map_size(image))
+        return x.view(1, M), y.view(1, M)
+
+    def _capture(self, image, rnd, return_color, amp, key):
         self._graph = self._graph_key = None
-        static = (image.clone(), x.clone(), y.clone())
+        mode, M = key[-1], key[2]
+        static = (image.clone(), tuple(r.clone() for r in rnd))
+
+        def body(enc):
+            x, y = self._centres(static[0], M, mode, static[1])
+            return self._ingest(static[0], x, y, return_color, enc)
         side = torch.cuda.Stream(device=image.device)
         side.wait_stream(torch.cuda.current_stream(image.device))
         dt = key[5] or torch.float16
@@ -376,12 +436,13 @@ class Patchifier(nn.Module):
             enc = tuple(copy.deepcopy(m).to(dt) for m in (self.fnet, self.inet))
         with torch.cuda.stream(side), torch.autocast("cuda", dtype=dt, enabled=amp, cache_enabled=False):
             for _ in range(2):  # warm-up: MIOpen solver selection, allocator pools
-                self._ingest(*static, return_color, enc)
+                body(enc)
         torch.cuda.current_stream(image.device).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph), torch.autocast("cuda", dtype=dt, enabled=amp, cache_enabled=False):
-            out = self._ingest(*static, return_color, enc)
+            out = body(enc)
         self._graph, self._graph_key, self._g_in, self._g_out = graph, key, static, out
+        self._g_cells = self.last_mask_cells   # (mask mode: the graph's own count word)
         self._g_enc = enc   # the graph holds their parameters' addresses
 
 

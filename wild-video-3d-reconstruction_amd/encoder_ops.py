@@ -120,6 +120,57 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+def map_size(H_, W_):
+    """the stride-4 feature map of an H x W frame (conv1 s2, then layer2 s2)"""
+    return conv_out(conv_out(H_, 7, 2), 3, 2), conv_out(conv_out(W_, 7, 2), 3, 2)
+
+
+def select_gradient(image, x, y, M, return_scores=False):
+    """The Patchifier's gradient-biased centre choice (csrc/select.hip, one
+    launch): of the candidates (x, y) int64 [C] on the stride-4 map of the uint8
+    frame [3, H, W], the M with the largest image gradient, in ascending
+    (score, candidate index) order -> x, y int64 [M][, scores fp32 [C]]."""
+    H.on_gpu(image, x, y)
+    if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[0] != 3:
+        raise RuntimeError("select_gradient: image must be uint8 [3, H, W]")
+    image = image.contiguous()
+    x, y = H.idx64(x.reshape(-1)), H.idx64(y.reshape(-1))
+    if x.numel() != y.numel():
+        raise RuntimeError("select_gradient: x and y must have the same length")
+    C, M = x.numel(), int(M)
+    ox = H.empty(M, dtype=torch.int64, device=image.device)
+    oy = H.empty(M, dtype=torch.int64, device=image.device)
+    sc = H.empty(C, dtype=torch.float32, device=image.device) if return_scores else None
+    H.check(H.lib().dpvo_select_gradient(image.data_ptr(), image.shape[1], image.shape[2], x.data_ptr(), y.data_ptr(),
+                                         C, M, ox.data_ptr(), oy.data_ptr(), _ptr(sc), H.stream_of(image)))
+    return (ox, oy, sc) if return_scores else (ox, oy)
+
+
+def select_mask(mask, keys, M, h, w):
+    """The Patchifier's masked centre choice (csrc/select.hip, two launches, no
+    host read): mask uint8 [H, W] (nonzero = set), keys int32 [h * w] >= 0 ->
+    x, y int64 [M], the valid cells of the h x w stride-4 map in ascending
+    (key, cell) order (cyclically repeated when there are fewer than M), and
+    count int32 [1], the number of valid cells."""
+    H.on_gpu(mask, keys)
+    if mask.dtype != torch.uint8 or mask.dim() != 2:
+        raise RuntimeError("select_mask: mask must be uint8 [H, W]")
+    if (h, w) != map_size(*mask.shape):
+        raise RuntimeError(f"select_mask: ({h}, {w}) is not the stride-4 map of a {tuple(mask.shape)} mask")
+    if keys.dtype != torch.int32 or keys.numel() != h * w:
+        raise RuntimeError("select_mask: keys must be int32 [h * w]")
+    mask, keys, M = mask.contiguous(), keys.contiguous(), int(M)
+    dev = mask.device
+    ox = H.empty(M, dtype=torch.int64, device=dev)
+    oy = H.empty(M, dtype=torch.int64, device=dev)
+    count = H.empty(1, dtype=torch.int32, device=dev)
+    ws = H.empty(H.lib().dpvo_select_mask_workspace_bytes(h, w), dtype=torch.uint8, device=dev)
+    H.check(H.lib().dpvo_select_mask(mask.data_ptr(), mask.shape[0], mask.shape[1], h, w, keys.data_ptr(), M,
+                                     ox.data_ptr(), oy.data_ptr(), count.data_ptr(), ws.data_ptr(),
+                                     H.stream_of(mask)))
+    return ox, oy, count
+
+
 class NativeEncoders:
     """fnet + inet of a Patchifier on the HIP library.
 

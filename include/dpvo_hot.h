@@ -51,6 +51,8 @@ const char* dpvo_hot_build_info(void);
 
 /* ------------------------------------------------------------------------
  * altcorr -- replaces cuda_corr (reference dpvo/altcorr/correlation.cpp:57-62)
+ * (the forward in csrc/altcorr.hip, on the matrix cores in csrc/corrmfma.hip;
+ * dpvo_edge_order in csrc/groupby.hip; backward and patchify in csrc/patchify.hip)
  * --------------------------------------------------------------------- */
 
 /* cuda_corr.forward(fmap1, fmap2, coords, ii, jj, radius)

@@ -13,7 +13,7 @@ objs=""
 for f in csrc/*.hip; do
   b=$(basename "$f" .hip)
   [ "$b" = buildinfo ] && continue
-  ff=""; [ "$b" = altcorr ] && ff="-ffp-contract=off"
+  ff=""; case "$b" in altcorr|patchify) ff="-ffp-contract=off";; esac
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Wno-unused-result $ff "$@" -c "$f" -o "$out/obj/$b.o" &
   objs="$objs $out/obj/$b.o"
 done

@@ -1,4 +1,6 @@
-"""altcorr on the GPU (through the C ABI) vs the oracle / golden vectors.
+"""altcorr on the GPU (through the C ABI) vs the oracle / golden vectors:
+the forward kernels of csrc/altcorr.hip (shared rules in csrc/corr.hpp), the
+backward and patchify of csrc/patchify.hip.
 
 Bar: bit-exact.  The reference accumulates in c10::Half with per-op
 rounding; the HIP kernel emulates that exactly, so every fp16 output bit must

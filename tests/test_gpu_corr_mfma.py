@@ -1,4 +1,5 @@
-"""The matrix-core correlation (csrc/corrmfma.hip, DPVO.corr's default path)
+"""The matrix-core correlation (csrc/corrmfma.hip with the rules it shares in
+csrc/corr.hpp, DPVO.corr's default path; its edge order: csrc/groupby.hip)
 against the oracle.
 
 It is NOT bit-identical to the reference: the reference accumulates the 128

@@ -1,7 +1,8 @@
-// altcorr.hip -- patch <-> frame local correlation for gfx950.
+// altcorr.hip -- patch <-> frame local correlation for gfx950: the forward pass.
 //
 // Replaces the reference's cuda_corr extension
-// (dpvo/altcorr/correlation.cpp:57-62, correlation_kernel.cu).
+// (dpvo/altcorr/correlation.cpp:57-62, correlation_kernel.cu); its backward
+// and patchify functions are in patchify.hip.
 //
 // Arithmetic contract: for fp16 inputs the result is bit-identical to the
 // reference, whose kernel accumulates `s += f1*f2` in c10::Half (each product
@@ -12,30 +13,30 @@
 // the chain is emulated with packed fp16 VALU ops.  This file is compiled with
 // -ffp-contract=off: a fused multiply-add would change the bits.
 //
-// Fast path (fp16, radius 3, 3x3 patches, channel-last fmap, C % 8 == 0):
-//   one workgroup per (batch, edge); 128 lanes per pyramid level.  The nine
-//   8x8 windows of a patch overlap: when their floor() offsets spread by at
-//   most 2 pixels they lie in one 10x10 box.  Lane u owns box pixel u, streams
-//   its C channels from HBM exactly once (16-byte loads), and runs the
-//   reference's fp16 chain for all nine patch pixels at once, two chains per
-//   packed op: (f1[p][c], f1[p'][c]) x (W[u][c], W[u][c]).  The per-pixel raw
-//   8x8 tiles are then gathered from LDS, bilinearly combined with the
-//   reference's exact rounding sequence and written in the caller's layout.
-//   Boxes wider than 10x10 fall back, inside the same kernel, to one 8x8
-//   window per patch pixel.
+// Exact kernel, v3 (fp16, radius 3, 3x3 patches, channel-last fmap, C = 128):
+//   one workgroup per (batch, edge): 128 threads for one pyramid level, 192
+//   for two.  The nine 8x8 windows of a patch overlap: when their floor()
+//   offsets spread by at most 4 pixels they lie in one box of at most 12x12
+//   (corr::patch_box).  The box pixels of the levels form one list of slots,
+//   walked a workgroup's width per pass.  A thread streams its pixel's 128
+//   channels from HBM exactly once (16-byte loads) and runs the reference's
+//   fp16 chain for all nine patch pixels at once, two chains per packed op:
+//   (f1[p][c], f1[p'][c]) x (W[u][c], W[u][c]).  The patch features are uniform
+//   over the workgroup, so they are SCALAR operands (s_load) from a packed
+//   table: the caller's (dpvo_corr_pack), or packed per call into
+//   stream-ordered scratch.  The raw tiles go to LDS; the epilogue gathers each
+//   pixel's 8x8 window from them, combines it bilinearly in the reference's
+//   exact rounding sequence (corr::bilinear) and writes the caller's layout.
+//   A level whose floors spread further falls back, inside the same kernel, to
+//   one 8x8 window per patch pixel (9 x 64 slots).
+//
+// Generic kernel: any float dtype / radius / patch size / strides, one thread
+// per output element.
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "corr.hpp"
 
 namespace dpvo {
-
-namespace corr {
-constexpr int R = 3, D = 8, DO = 7, PS = 3, NP = 9, NPAIR = 5;
-// v3's shared box: floor spreads up to 4 px (12 x 12).  At level 1 about 1 edge
-// in 9 of the C3 workload spreads by 3 px (perspective scale ~1.4 between
-// frames up to 35 apart); per-pixel windows would cost it 4x the common pass.
-constexpr int SBOX = 12;
-}
 
 struct CorrFastParams {
     const half_t* gmap;
@@ -55,13 +56,12 @@ struct CorrFastParams {
     const uint32_t* f1tab;   // [B*N1][C][5] packed patch-feature pairs (corr_pack_kernel)
 };
 
+namespace {
+
+constexpr int NPAIR = 5;   // the nine patch pixels as half2 pairs: (p0,p1) .. (p8,0)
+
 __device__ __forceinline__ half2_t as_h2(uint32_t v) { return __builtin_bit_cast(half2_t, v); }
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-
-// exact binary16 ops (contraction is off for this file)
-__device__ __forceinline__ half_t hmul(half_t a, half_t b) { return a * b; }
-__device__ __forceinline__ half_t hadd(half_t a, half_t b) { return a + b; }
 
 // Block -> edge map that gives each XCD a contiguous run of edges (blocks
 // b, b+8, ... share an XCD under round-robin dispatch), so consecutive edges --
@@ -115,18 +115,22 @@ __global__ __launch_bounds__(256) void corr_pack_kernel(const half_t* __restrict
     }
 }
 
+}  // namespace
+
+// (In dpvo, not in the anonymous namespace like every other kernel here: with internal linkage the compiler
+// lays the three LDS arrays of the one-level instance out in another order, which changes its instructions.)
 template <int NLEV, int C8>
 __global__ __launch_bounds__(FastThreads<NLEV>::value) void corr_sfast_kernel(CorrFastParams p)
 {
     using namespace corr;
     constexpr int NT = FastThreads<NLEV>::value;
     constexpr int C = C8 * 8;
-    __shared__ half_t raw[NLEV][NP][SBOX * SBOX];
+    __shared__ half_t raw[NLEV][NP][BOX * BOX];
     __shared__ LevelMeta meta[NLEV];
     // per (patch pixel, level): the reference's bilinear weights (each product
     // rounded to binary16 exactly as correlation_kernel.cu:221-232 forms them)
     // and the raw-tile offset of the window origin
-    struct EpiQ { half_t w00, w01, w10, w11; int base, bw; };
+    struct EpiQ { Bilinear<half_t> w; int base, bw; };
     __shared__ EpiQ epq[NP * NLEV];
 
     const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
@@ -157,11 +161,7 @@ __global__ __launch_bounds__(FastThreads<NLEV>::value) void corr_sfast_kernel(Co
             ymin = min(ymin, m.fy[q]); ymax = max(ymax, m.fy[q]);
             xmin = min(xmin, m.fx[q]); xmax = max(xmax, m.fx[q]);
         }
-        m.fast = ((int64_t)ymax - ymin) <= SBOX - D && ((int64_t)xmax - xmin) <= SBOX - D;
-        m.oy = wrap_add(ymin, -R);
-        m.ox = wrap_add(xmin, -R);
-        m.bh = m.fast ? (ymax - ymin) + D : D;
-        m.bw = m.fast ? (xmax - xmin) + D : D;
+        patch_box(m, ymin, ymax, xmin, xmax);
         m.nslots = m.fast ? m.bh * m.bw : NP * D * D;
         m.rbw = 1.0f / (float)m.bw;
     }
@@ -172,16 +172,12 @@ __global__ __launch_bounds__(FastThreads<NLEV>::value) void corr_sfast_kernel(Co
         const int bw = m.fast ? m.bw : D;
         const int oy = m.fast ? m.fy[q] - (int)wrap_add(m.oy, R) : 0;
         const int ox = m.fast ? m.fx[q] - (int)wrap_add(m.ox, R) : 0;
-        const float xq = m.xs[q], yq = m.ys[q];
-        const half_t dx = (half_t)(xq - floorf(xq));
-        const half_t dy = (half_t)(yq - floorf(yq));
-        const half_t one = (half_t)1.0f;
-        const half_t omdx = one - dx, omdy = one - dy;
         EpiQ& t = epq[tid];
-        t.w00 = hmul(omdx, omdy);
-        t.w01 = hmul(dx, omdy);
-        t.w10 = hmul(omdx, dy);
-        t.w11 = hmul(dx, dy);
+        const Bilinear<half_t> w = bilinear_weights<half_t>(m.xs[q], m.ys[q]);
+        t.w.w00 = w.w00;   // (field by field: assigned as one aggregate the four stores merge into another instruction)
+        t.w.w01 = w.w01;
+        t.w.w10 = w.w10;
+        t.w.w11 = w.w11;
         t.base = oy * bw + ox;
         t.bw = bw;
     }
@@ -204,11 +200,12 @@ __global__ __launch_bounds__(FastThreads<NLEV>::value) void corr_sfast_kernel(Co
         } else {
             const int q = loc / (D * D), u = loc - q * (D * D);
             const int uy = u / D, ux = u - uy * D;
-            gy = wrap_add(m.fy[q], uy - R); gx = wrap_add(m.fx[q], ux - R);
+            gy = window_px(m.fy[q], uy, R); gx = window_px(m.fx[q], ux, R);
             s.q_only = q;
             s.u = u;
         }
         const int lv = s.lev;
+        // (corr::in_map written out: as a call, in any of three forms, it changes this kernel's branch code)
         s.inb = s.act && ix_ok && jx >= 0 && jx < p.N2[lv] && gy >= 0 && gy < p.H2[lv] && gx >= 0 && gx < p.W2[lv];
         const half_t* base = p.fmap[lv] + b * p.f_s0[lv];
         s.ptr = reinterpret_cast<const uint4*>(
@@ -314,15 +311,15 @@ __global__ __launch_bounds__(FastThreads<NLEV>::value) void corr_sfast_kernel(Co
                          ((uintptr_t)ob & 3) == 0;
     if (stacked) {
         for (int t = tid; t < DO * DO * NP; t += NT) {
-            const int pos = t / NP, q = t - pos * NP;
-            const int bx = pos / DO, a = pos - bx * DO;
-            const EpiQ t0 = epq[q * NLEV], t1 = epq[q * NLEV + 1];
-            const half_t* c0 = &raw[0][q][t0.base + a * t0.bw + bx];
-            const half_t* c1 = &raw[NLEV - 1][q][t1.base + a * t1.bw + bx];
-            half2_t v = half2_t{t0.w00, t1.w00} * half2_t{c0[0], c1[0]};
-            v = v + half2_t{t0.w01, t1.w01} * half2_t{c0[1], c1[1]};
-            v = v + half2_t{t0.w10, t1.w10} * half2_t{c0[t0.bw], c1[t1.bw]};
-            v = v + half2_t{t0.w11, t1.w11} * half2_t{c0[t0.bw + 1], c1[t1.bw + 1]};
+            const StackedPos s = stacked_pos(t);
+            const EpiQ t0 = epq[s.q * NLEV], t1 = epq[s.q * NLEV + 1];
+            const half_t* c0 = &raw[0][s.q][t0.base + s.a * t0.bw + s.bx];
+            const half_t* c1 = &raw[NLEV - 1][s.q][t1.base + s.a * t1.bw + s.bx];
+            // (corr::bilinear's chain for half2_t written out: as a call the packed products are scheduled differently)
+            half2_t v = half2_t{t0.w.w00, t1.w.w00} * half2_t{c0[0], c1[0]};
+            v = v + half2_t{t0.w.w01, t1.w.w01} * half2_t{c0[1], c1[1]};
+            v = v + half2_t{t0.w.w10, t1.w.w10} * half2_t{c0[t0.bw], c1[t1.bw]};
+            v = v + half2_t{t0.w.w11, t1.w.w11} * half2_t{c0[t0.bw + 1], c1[t1.bw + 1]};
             *(half2_t*)(ob + 2 * t) = v;
         }
         return;
@@ -336,16 +333,14 @@ __global__ __launch_bounds__(FastThreads<NLEV>::value) void corr_sfast_kernel(Co
         const half_t* rt = &raw[lev][q][t.base];
         half_t* oq = ob + q * p.o_p + lev * p.o_l;
         for (int pos = g; pos < DO * DO; pos += GR) {
-            const int bx = pos / DO, a = pos - bx * DO;
-            const half_t* c = rt + a * t.bw + bx;
-            half_t v = hmul(t.w00, c[0]);
-            v = hadd(v, hmul(t.w01, c[1]));
-            v = hadd(v, hmul(t.w10, c[t.bw]));
-            v = hadd(v, hmul(t.w11, c[t.bw + 1]));
-            oq[bx * p.o_x + a * p.o_y] = v;
+            const WindowPos wp = window_pos(pos);
+            const half_t* c = rt + wp.a * t.bw + wp.bx;
+            oq[wp.bx * p.o_x + wp.a * p.o_y] = bilinear<half_t>(t.w, c[0], c[1], c[t.bw], c[t.bw + 1]);
         }
     }
 }
+
+namespace {
 
 // ---------------------------------------------------------------------------
 // generic path: any float dtype / radius / patch size / strides.
@@ -380,10 +375,10 @@ __device__ __forceinline__ double chain_step<double>(double s, double a, double 
 template <typename T>
 __device__ T raw_corr(const CorrGenParams& p, int b, int ix, int jx, int i0, int j0, int fy, int fx, int a, int c)
 {
-    const int i1 = wrap_add(fy, a - p.radius), j1 = wrap_add(fx, c - p.radius);
+    const int i1 = corr::window_px(fy, a, p.radius), j1 = corr::window_px(fx, c, p.radius);
     T s = (T)0;
     if (ix < 0 || ix >= p.N1 || jx < 0 || jx >= p.N2) return s;
-    if (!(i1 >= 0 && i1 < p.H2 && j1 >= 0 && j1 < p.W2)) return s;
+    if (!corr::in_map(i1, j1, p.H2, p.W2)) return s;
     const T* f1 = (const T*)p.gmap + b * p.g_s[0] + (int64_t)ix * p.g_s[1] + i0 * p.g_s[3] + j0 * p.g_s[4];
     const T* f2 = (const T*)p.fmap + b * p.f_s[0] + (int64_t)jx * p.f_s[1] + (int64_t)i1 * p.f_s[3] + (int64_t)j1 * p.f_s[4];
     for (int k = 0; k < p.C; k++) s = chain_step<T>(s, f1[k * p.g_s[2]], f2[k * p.f_s[2]]);
@@ -411,132 +406,41 @@ __global__ __launch_bounds__(256) void corr_generic_kernel(CorrGenParams p)
         const T c01 = raw_corr<T>(p, b, ix, jx, i0, j0, fy, fx, a, bx + 1);
         const T c10 = raw_corr<T>(p, b, ix, jx, i0, j0, fy, fx, a + 1, bx);
         const T c11 = raw_corr<T>(p, b, ix, jx, i0, j0, fy, fx, a + 1, bx + 1);
-        const T dx = (T)(x - floorf(x)), dy = (T)(y - floorf(y));
-        const T one = (T)1;
-        const T omdx = one - dx, omdy = one - dy;
-        T v = (omdx * omdy) * c00;
-        v = v + (dx * omdy) * c01;
-        v = v + (omdx * dy) * c10;
-        v = v + (dx * dy) * c11;
-        ((T*)p.out)[b * p.o_b + (int64_t)e * p.o_e + bx * p.o_x + a * p.o_y + i0 * p.o_i + j0 * p.o_j] = v;
+        ((T*)p.out)[b * p.o_b + (int64_t)e * p.o_e + bx * p.o_x + a * p.o_y + i0 * p.o_i + j0 * p.o_j] =
+            corr::bilinear<T>(corr::bilinear_weights<T>(x, y), c00, c01, c10, c11);
     }
 }
 
 // ---------------------------------------------------------------------------
-// backward (training surface): atomics into fp32/fp64 grads
+// host side
 // ---------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void corr_backward_kernel(const T* gmap, int N1, int C, int PH, int PW,
-                                                            const T* fmap, int N2, int H2, int W2,
-                                                            const float* coords, const int64_t* ii,
-                                                            const int64_t* jj, const float* grad, int B, int E,
-                                                            int radius, T* g1, T* g2, int64_t total)
-{
-    const int D = 2 * radius + 2, Do = D - 1;
-    for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        int64_t n = idx;
-        const int j0 = n % PW; n /= PW;
-        const int i0 = n % PH; n /= PH;
-        const int c = n % D; n /= D;   // x offset in the raw window
-        const int a = n % D; n /= D;   // y offset
-        const int e = n % E; n /= E;
-        const int b = (int)n;
-        const float* cb = coords + (((int64_t)b * E + e) * 2) * PH * PW + i0 * PW + j0;
-        const float x = cb[0], y = cb[PH * PW];
-        const float dx = x - floorf(x), dy = y - floorf(y);
-        // raw-window gradient = sum of the bilinear taps that read (a, c)
-        float g = 0.f;
-        auto G = [&](int aa, int cc) -> float {
-            if (aa < 0 || aa >= Do || cc < 0 || cc >= Do) return 0.f;
-            // grad layout: [B][E][x][y][PH][PW]
-            return grad[((((int64_t)b * E + e) * Do + cc) * Do + aa) * PH * PW + i0 * PW + j0];
-        };
-        g += (1 - dx) * (1 - dy) * G(a, c);
-        g += dx * (1 - dy) * G(a, c - 1);
-        g += (1 - dx) * dy * G(a - 1, c);
-        g += dx * dy * G(a - 1, c - 1);
-        if (g == 0.f) continue;
-        const int ix = (int)ii[e], jx = (int)jj[e];
-        if (ix < 0 || ix >= N1 || jx < 0 || jx >= N2) continue;
-        const int i1 = wrap_add(floor_to_int_sat(y), a - radius), j1 = wrap_add(floor_to_int_sat(x), c - radius);
-        if (!(i1 >= 0 && i1 < H2 && j1 >= 0 && j1 < W2)) continue;
-        const T* f1 = gmap + (((int64_t)b * N1 + ix) * C) * PH * PW + i0 * PW + j0;
-        const T* f2 = fmap + (((int64_t)b * N2 + jx) * C) * H2 * W2 + (int64_t)i1 * W2 + j1;
-        T* d1 = g1 + (((int64_t)b * N1 + ix) * C) * PH * PW + i0 * PW + j0;
-        T* d2 = g2 + (((int64_t)b * N2 + jx) * C) * H2 * W2 + (int64_t)i1 * W2 + j1;
-        for (int k = 0; k < C; k++) {
-            atomicAdd(d1 + (int64_t)k * PH * PW, (T)g * f2[(int64_t)k * H2 * W2]);
-            atomicAdd(d2 + (int64_t)k * H2 * W2, (T)g * f1[(int64_t)k * PH * PW]);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// patchify
-// ---------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void patchify_forward_kernel(const T* net, int64_t s0, int64_t s1, int64_t s2,
-                                                               int64_t s3, int B, int C, int H, int W,
-                                                               const float* coords, int M, int radius, T* out,
-                                                               int64_t total)
-{
-    const int D = 2 * radius + 2;
-    for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        int64_t n = idx;
-        const int bb = n % D; n /= D;
-        const int a = n % D; n /= D;
-        const int k = n % C; n /= C;
-        const int m = n % M; n /= M;
-        const int b = (int)n;
-        const float x = coords[((int64_t)b * M + m) * 2 + 0], y = coords[((int64_t)b * M + m) * 2 + 1];
-        const int i = wrap_add(floor_to_int_sat(y), a - radius), j = wrap_add(floor_to_int_sat(x), bb - radius);
-        T v = (T)0;
-        if (i >= 0 && i < H && j >= 0 && j < W) v = net[b * s0 + k * s1 + (int64_t)i * s2 + (int64_t)j * s3];
-        out[idx] = v;
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void patchify_backward_kernel(int B, int C, int H, int W, const float* coords,
-                                                                int M, int radius, const T* grad, T* net_grad,
-                                                                int64_t total)
-{
-    const int D = 2 * radius + 2;
-    for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        int64_t n = idx;
-        const int bb = n % D; n /= D;
-        const int a = n % D; n /= D;
-        const int k = n % C; n /= C;
-        const int m = n % M; n /= M;
-        const int b = (int)n;
-        const float x = coords[((int64_t)b * M + m) * 2 + 0], y = coords[((int64_t)b * M + m) * 2 + 1];
-        const int i = wrap_add(floor_to_int_sat(y), a - radius), j = wrap_add(floor_to_int_sat(x), bb - radius);
-        if (i >= 0 && i < H && j >= 0 && j < W)
-            atomicAdd(net_grad + (((int64_t)b * C + k) * H + i) * W + j, grad[idx]);
-    }
-}
-
-}  // namespace dpvo
-
-using namespace dpvo;
-
-namespace {
-
 bool fast_path_ok(int dtype, const int64_t* gsz, const int64_t* fsz, const int64_t* fst, const int64_t* csz,
                   int radius)
 {
     if (dtype != DPVO_F16 || radius != corr::R) return false;
     if (gsz[3] != corr::PS || gsz[4] != corr::PS || csz[3] != corr::PS || csz[4] != corr::PS) return false;
-    if (gsz[2] != 128 || fsz[2] != gsz[2]) return false;
-    if (fst[2] != 1) return false;  // channel-last storage
-    if (fst[0] % 8 || fst[1] % 8 || fst[3] % 8 || fst[4] % 8) return false;  // 16-byte aligned pixels
-    return true;
+    if (gsz[2] != corr::C || fsz[2] != gsz[2]) return false;
+    return corr::channel_last_16b(fst) && fst[0] % 8 == 0;
 }
 
-int launch_fast(int nlev, const void* gmap, const int64_t* gsz, const int64_t* gst, const void* const* fmaps,
+// the scalar-operand table of gmap [B][N1][C][3][3]: its size, and corr_pack_kernel over it
+size_t table_bytes(const int64_t* gsz) { return (size_t)(gsz[0] * gsz[1] * gsz[2]) * 5 * 4; }
+
+void pack_table(const void* gmap, const int64_t* gsz, const int64_t* gst, void* tab, hipStream_t stream)
+{
+    const int64_t np = gsz[0] * gsz[1] * gsz[2];
+    hipLaunchKernelGGL(corr_pack_kernel, dim3(grid_for(np, 256, 8192)), dim3(256), 0, stream, (const half_t*)gmap,
+                       gst[0], gst[1], gst[2], gst[3], gst[4], (int)gsz[0], (int)gsz[1], (int)gsz[2], (uint32_t*)tab);
+}
+
+// what became of a fast-path request: on anything but Done the caller runs the generic kernel
+enum class Fast {
+    Done,         // launched (or nothing to do)
+    Misaligned,   // a feature map's base is not 16-byte aligned
+    NoScratch,    // no stream-ordered scratch for the table
+};
+
+Fast launch_fast(int nlev, const void* gmap, const int64_t* gsz, const int64_t* gst, const void* const* fmaps,
                 const int64_t* fsz, const int64_t* fst, const float* scales, const float* coords, const int64_t* csz,
                 const int64_t* cst, const int64_t* ii, const int64_t* jj, void* out, const int64_t* ostr,
                 hipStream_t stream, const void* table = nullptr)
@@ -552,7 +456,7 @@ int launch_fast(int nlev, const void* gmap, const int64_t* gsz, const int64_t* g
     p.B = (int)csz[0];
     p.E = (int)csz[1];
     for (int l = 0; l < nlev; l++) {
-        if (reinterpret_cast<uintptr_t>(fmaps[l]) % 16) return 1;  // not 16-byte aligned: caller falls back
+        if (reinterpret_cast<uintptr_t>(fmaps[l]) % 16) return Fast::Misaligned;
         p.fmap[l] = (const half_t*)fmaps[l];
         p.f_s0[l] = fst[l * 5 + 0];
         p.f_s1[l] = fst[l * 5 + 1];
@@ -566,30 +470,23 @@ int launch_fast(int nlev, const void* gmap, const int64_t* gsz, const int64_t* g
     p.out = (half_t*)out;
     p.o_b = ostr[0]; p.o_e = ostr[1]; p.o_l = ostr[2]; p.o_x = ostr[3]; p.o_y = ostr[4]; p.o_p = ostr[5];
     const int64_t nblk = (int64_t)p.B * p.E;
-    if (nblk == 0) return 0;
-    {
-        // patch features as a scalar-load table: the caller's (dpvo_corr_pack), or
-        // packed here into stream-ordered scratch
-        void* tab = nullptr;
-        if (table) {
-            p.f1tab = (const uint32_t*)table;
-        } else {
-            const size_t tab_bytes = (size_t)p.B * p.N1 * p.C * 5 * 4;
-            if (hipMallocAsync(&tab, tab_bytes, stream) != hipSuccess) return 2;
-            const int64_t np = (int64_t)p.B * p.N1 * p.C;
-            hipLaunchKernelGGL(corr_pack_kernel, dim3(grid_for(np, 256, 8192)), dim3(256), 0, stream, p.gmap,
-                               p.g_s[0], p.g_s[1], p.g_s[2], p.g_s[3], p.g_s[4], p.B, p.N1, p.C, (uint32_t*)tab);
-            p.f1tab = (const uint32_t*)tab;
-        }
-        if (nlev == 2)
-            hipLaunchKernelGGL((corr_sfast_kernel<2, 16>), dim3((unsigned)nblk), dim3(FastThreads<2>::value), 0,
-                               stream, p);
-        else
-            hipLaunchKernelGGL((corr_sfast_kernel<1, 16>), dim3((unsigned)nblk), dim3(FastThreads<1>::value), 0,
-                               stream, p);
-        if (tab) (void)hipFreeAsync(tab, stream);
+    if (nblk == 0) return Fast::Done;
+    // patch features as a scalar-load table: the caller's (dpvo_corr_pack), or
+    // packed here into stream-ordered scratch
+    void* tab = nullptr;
+    if (!table) {
+        if (hipMallocAsync(&tab, table_bytes(gsz), stream) != hipSuccess) return Fast::NoScratch;
+        pack_table(gmap, gsz, gst, tab, stream);
     }
-    return 0;
+    p.f1tab = (const uint32_t*)(table ? table : tab);
+    if (nlev == 2)
+        hipLaunchKernelGGL((corr_sfast_kernel<2, 16>), dim3((unsigned)nblk), dim3(FastThreads<2>::value), 0, stream,
+                           p);
+    else
+        hipLaunchKernelGGL((corr_sfast_kernel<1, 16>), dim3((unsigned)nblk), dim3(FastThreads<1>::value), 0, stream,
+                           p);
+    if (tab) (void)hipFreeAsync(tab, stream);
+    return Fast::Done;
 }
 
 int launch_generic(int dtype, const void* gmap, const int64_t* gsz, const int64_t* gst, const void* fmap,
@@ -611,12 +508,9 @@ int launch_generic(int dtype, const void* gmap, const int64_t* gsz, const int64_
     p.total = (int64_t)p.B * p.E * Do * Do * p.PH * p.PW;
     if (p.total == 0) return 0;
     const unsigned grid = grid_for(p.total, 256, 65536);
-    if (dtype == DPVO_F16)
-        hipLaunchKernelGGL(corr_generic_kernel<half_t>, dim3(grid), dim3(256), 0, stream, p);
-    else if (dtype == DPVO_F32)
-        hipLaunchKernelGGL(corr_generic_kernel<float>, dim3(grid), dim3(256), 0, stream, p);
-    else
-        hipLaunchKernelGGL(corr_generic_kernel<double>, dim3(grid), dim3(256), 0, stream, p);
+    corr::dispatch_dtype(dtype, [&](auto t) {   // (check_common: one of the three)
+        hipLaunchKernelGGL(corr_generic_kernel<decltype(t)>, dim3(grid), dim3(256), 0, stream, p);
+    });
     return 0;
 }
 
@@ -632,6 +526,9 @@ int check_common(int dtype, const void* gmap, const int64_t* gsz, const int64_t*
 }
 
 }  // namespace
+}  // namespace dpvo
+
+using namespace dpvo;
 
 extern "C" int dpvo_corr_forward(int dtype, const void* gmap, const int64_t* gmap_size, const int64_t* gmap_stride,
                                  const void* fmap, const int64_t* fmap_size, const int64_t* fmap_stride,
@@ -649,9 +546,11 @@ extern "C" int dpvo_corr_forward(int dtype, const void* gmap, const int64_t* gma
         const int64_t ostr[6] = {E * Do * Do * P2, Do * Do * P2, 0, P2, Do * P2, 1};
         const void* fm[1] = {fmap};
         const float sc[1] = {1.0f};
-        const int rc = launch_fast(1, gmap, gmap_size, gmap_stride, fm, fmap_size, fmap_stride, sc, coords,
-                                   coords_size, coords_stride, ii, jj, corr, ostr, as_stream(stream));
-        if (rc == 0) { DPVO_CHECK_LAUNCH(); return 0; }
+        if (launch_fast(1, gmap, gmap_size, gmap_stride, fm, fmap_size, fmap_stride, sc, coords, coords_size,
+                        coords_stride, ii, jj, corr, ostr, as_stream(stream)) == Fast::Done) {
+            DPVO_CHECK_LAUNCH();
+            return 0;
+        }
     }
     const int64_t ostr[6] = {E * Do * Do * P2, Do * Do * P2, P2, Do * P2, coords_size[4], 1};
     launch_generic(dtype, gmap, gmap_size, gmap_stride, fmap, fmap_size, fmap_stride, 1.0f, coords, coords_size,
@@ -696,9 +595,11 @@ extern "C" int dpvo_corr_forward_pyramid_ld(int dtype, const void* gmap, const i
                    fmap_sizes[5 * l] == coords_size[0];
     if (all_fast) {
         const int64_t ostr[6] = {E * o_e, o_e, 1, Do * P2 * nlev, P2 * nlev, nlev};
-        const int rc = launch_fast(nlev, gmap, gmap_size, gmap_stride, fmaps, fmap_sizes, fmap_strides, level_scale,
-                                   coords, coords_size, coords_stride, ii, jj, corr, ostr, as_stream(stream), table);
-        if (rc == 0) { DPVO_CHECK_LAUNCH(); return 0; }
+        if (launch_fast(nlev, gmap, gmap_size, gmap_stride, fmaps, fmap_sizes, fmap_strides, level_scale, coords,
+                        coords_size, coords_stride, ii, jj, corr, ostr, as_stream(stream), table) == Fast::Done) {
+            DPVO_CHECK_LAUNCH();
+            return 0;
+        }
     }
     for (int l = 0; l < nlev; l++) {
         DPVO_CHECK_ARG(fmap_sizes[5 * l] == coords_size[0] && fmap_sizes[5 * l + 2] == gmap_size[2],
@@ -714,75 +615,9 @@ extern "C" int dpvo_corr_forward_pyramid_ld(int dtype, const void* gmap, const i
     return 0;
 }
 
-extern "C" int dpvo_corr_backward(int dtype, const void* gmap, const int64_t* gsz, const void* fmap,
-                                  const int64_t* fsz, const float* coords, const int64_t* csz, const int64_t* ii,
-                                  const int64_t* jj, const float* grad, int radius, void* gmap_grad, void* fmap_grad,
-                                  void* stream)
-{
-    DPVO_CHECK_ARG(dtype == DPVO_F32 || dtype == DPVO_F64, "backward supports float32/float64 feature maps");
-    DPVO_CHECK_ARG(csz[2] == 2 && radius >= 0, "bad coords / radius");
-    const int D = 2 * radius + 2;
-    const int64_t total = csz[0] * csz[1] * D * D * csz[3] * csz[4];
-    if (total == 0) return 0;
-    const unsigned grid = grid_for(total, 256, 65536);
-    if (dtype == DPVO_F32)
-        hipLaunchKernelGGL(corr_backward_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream),
-                           (const float*)gmap, (int)gsz[1], (int)gsz[2], (int)csz[3], (int)csz[4],
-                           (const float*)fmap, (int)fsz[1], (int)fsz[3], (int)fsz[4], coords, ii, jj, grad,
-                           (int)csz[0], (int)csz[1], radius, (float*)gmap_grad, (float*)fmap_grad, total);
-    else
-        hipLaunchKernelGGL(corr_backward_kernel<double>, dim3(grid), dim3(256), 0, as_stream(stream),
-                           (const double*)gmap, (int)gsz[1], (int)gsz[2], (int)csz[3], (int)csz[4],
-                           (const double*)fmap, (int)fsz[1], (int)fsz[3], (int)fsz[4], coords, ii, jj, grad,
-                           (int)csz[0], (int)csz[1], radius, (double*)gmap_grad, (double*)fmap_grad, total);
-    DPVO_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int dpvo_patchify_forward(int dtype, const void* net, const int64_t* nsz, const int64_t* nst,
-                                     const float* coords, int64_t M, int radius, void* out, void* stream)
-{
-    DPVO_CHECK_ARG(radius >= 0 && radius <= 64, "bad radius");
-    const int D = 2 * radius + 2;
-    const int64_t total = nsz[0] * M * nsz[1] * D * D;
-    if (total == 0) return 0;
-    const unsigned grid = grid_for(total, 256, 65536);
-#define PF_LAUNCH(T)                                                                                        \
-    hipLaunchKernelGGL(patchify_forward_kernel<T>, dim3(grid), dim3(256), 0, as_stream(stream), (const T*)net, \
-                       nst[0], nst[1], nst[2], nst[3], (int)nsz[0], (int)nsz[1], (int)nsz[2], (int)nsz[3], coords, \
-                       (int)M, radius, (T*)out, total)
-    if (dtype == DPVO_F16) PF_LAUNCH(half_t);
-    else if (dtype == DPVO_F32) PF_LAUNCH(float);
-    else if (dtype == DPVO_F64) PF_LAUNCH(double);
-    else DPVO_CHECK_ARG(false, "unsupported dtype");
-#undef PF_LAUNCH
-    DPVO_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int dpvo_patchify_backward(int dtype, const int64_t* nsz, const float* coords, int64_t M, int radius,
-                                      const void* grad, void* net_grad, void* stream)
-{
-    DPVO_CHECK_ARG(dtype == DPVO_F32 || dtype == DPVO_F64, "patchify backward supports float32/float64");
-    const int D = 2 * radius + 2;
-    const int64_t total = nsz[0] * M * nsz[1] * D * D;
-    if (total == 0) return 0;
-    const unsigned grid = grid_for(total, 256, 65536);
-    if (dtype == DPVO_F32)
-        hipLaunchKernelGGL(patchify_backward_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream),
-                           (int)nsz[0], (int)nsz[1], (int)nsz[2], (int)nsz[3], coords, (int)M, radius,
-                           (const float*)grad, (float*)net_grad, total);
-    else
-        hipLaunchKernelGGL(patchify_backward_kernel<double>, dim3(grid), dim3(256), 0, as_stream(stream),
-                           (int)nsz[0], (int)nsz[1], (int)nsz[2], (int)nsz[3], coords, (int)M, radius,
-                           (const double*)grad, (double*)net_grad, total);
-    DPVO_CHECK_LAUNCH();
-    return 0;
-}
-
 extern "C" size_t dpvo_corr_table_bytes(const int64_t* gmap_size)
 {
-    return (size_t)(gmap_size[0] * gmap_size[1] * gmap_size[2]) * 5 * 4;
+    return table_bytes(gmap_size);
 }
 
 extern "C" int dpvo_corr_pack(const void* gmap, const int64_t* gmap_size, const int64_t* gmap_stride, void* table,
@@ -791,11 +626,8 @@ extern "C" int dpvo_corr_pack(const void* gmap, const int64_t* gmap_size, const 
     DPVO_CHECK_ARG(gmap && table, "null pointer");
     DPVO_CHECK_ARG(gmap_size[3] == 3 && gmap_size[4] == 3, "the packed table is for 3x3 patches");
     DPVO_CHECK_ARG(((uintptr_t)table & 15) == 0, "table must be 16-byte aligned");
-    const int64_t np = gmap_size[0] * gmap_size[1] * gmap_size[2];
-    if (np == 0) return 0;
-    hipLaunchKernelGGL(corr_pack_kernel, dim3(grid_for(np, 256, 8192)), dim3(256), 0, as_stream(stream),
-                       (const half_t*)gmap, gmap_stride[0], gmap_stride[1], gmap_stride[2], gmap_stride[3],
-                       gmap_stride[4], (int)gmap_size[0], (int)gmap_size[1], (int)gmap_size[2], (uint32_t*)table);
+    if (table_bytes(gmap_size) == 0) return 0;
+    pack_table(gmap, gmap_size, gmap_stride, table, as_stream(stream));
     DPVO_CHECK_LAUNCH();
     return 0;
 }

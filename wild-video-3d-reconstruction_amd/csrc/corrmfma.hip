@@ -26,12 +26,10 @@
 #include "corrmfma.hpp"
 
 namespace dpvo {
-
+namespace {
 
 typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
 typedef float f4m_t __attribute__((ext_vector_type(4)));
-
-
 
 __device__ __forceinline__ void cm_wave_fence()
 {
@@ -115,7 +113,7 @@ __device__ __forceinline__ CmEdgeIn cm_load_edge(const CorrMfmaParams& p, int sl
     in.e = p.order ? ((cm_cint*)p.order)[slot] : slot;
     in.ix = (int)((cm_cint64*)p.ii)[in.e];
     in.jx = (int)((cm_cint64*)p.jj)[in.e];
-    const int q = q16 < cm::NP ? q16 : 0;
+    const int q = q16 < corr::NP ? q16 : 0;
     const float* cb = p.coords + (int64_t)in.e * p.c_s[1] + (q / 3) * p.c_s[3] + (q % 3) * p.c_s[4];
     in.cx = cb[0];
     in.cy = cb[p.c_s[2]];
@@ -135,7 +133,7 @@ struct CmLevel {
     const char* frame;    // this target frame's map (byte pointer), wave-uniform
     int64_t rowb;         // row stride in bytes
     int H, W, pixb, frameext;
-    int fast, oy, ox, bw, npx, ntiles;
+    int fast, oy, ox, bw, bh, npx, ntiles;
     int by, bx;           // per lane: box pixel (lane & 15) of the first tile (fast)
     int fy, fx;           // per lane: floors of patch pixel (lane & 15)
 };
@@ -157,6 +155,7 @@ struct CmLevel {
 __global__ __launch_bounds__(64 * cm::WAVES) void corr_mfma_kernel(CorrMfmaParams p)
 {
     using namespace cm;
+    using namespace corr;
     __shared__ __attribute__((aligned(16))) float raw[WAVES][2 * RL];
     __shared__ float wts[WAVES][2][4][16];   // bilinear weights per level and patch pixel
     __shared__ int ebase[WAVES][2][16];      // window origin of each patch pixel inside its raw row
@@ -173,12 +172,10 @@ __global__ __launch_bounds__(64 * cm::WAVES) void corr_mfma_kernel(CorrMfmaParam
     int eq[7], ex[7], ey[7];
 #pragma unroll
     for (int i = 0; i < 7; i++) {
-        const int t = min(lane + 64 * i, DO * DO * NP - 1);
-        const int pos = t / NP, q = t - pos * NP;
-        const int bxo = pos / DO, ay = pos - bxo * DO;
-        eq[i] = q;
-        ex[i] = bxo;
-        ey[i] = ay;
+        const StackedPos s = stacked_pos(min(lane + 64 * i, DO * DO * NP - 1));
+        eq[i] = s.q;
+        ex[i] = s.bx;
+        ey[i] = s.a;
     }
 
     CmEdgeIn nin = cm_load_edge(p, slot, q16);
@@ -226,16 +223,14 @@ __global__ __launch_bounds__(64 * cm::WAVES) void corr_mfma_kernel(CorrMfmaParam
             L.W = p.W2[l];
             L.pixb = p.pixb[l];
             L.frameext = jok && ix_ok ? p.frameext[l] : 0;
-            L.fast = ((int64_t)ymax - ymin) <= BOXMAX - D && ((int64_t)xmax - xmin) <= BOXMAX - D;
-            L.oy = wrap_add(ymin, -R);
-            L.ox = wrap_add(xmin, -R);
-            L.bw = L.fast ? xmax - xmin + D : D;
-            const int bh = L.fast ? ymax - ymin + D : D;
-            L.npx = L.bw * bh;
+            patch_box(L, ymin, ymax, xmin, xmax);
+            L.npx = L.bw * L.bh;
             L.ntiles = L.fast ? (L.npx + 15) / 16 : NP * 4;
             L.by = q16 / L.bw;
             L.bx = q16 - L.by * L.bw;
             if (lane < NP) {
+                // (corr::bilinear_weights<float>'s expressions written out: as a call, in either of two forms,
+                // these products land in other registers)
                 const float dx = x - floorf(x), dy = y - floorf(y);
                 wts[wave][l][0][lane] = (1.f - dx) * (1.f - dy);
                 wts[wave][l][1][lane] = dx * (1.f - dy);
@@ -249,6 +244,8 @@ __global__ __launch_bounds__(64 * cm::WAVES) void corr_mfma_kernel(CorrMfmaParam
 
         // ---- tiles of both levels: A = 16 box pixels (or two window rows), B = the patch.
         const int ntot = L0.ntiles + L1.ntiles;
+        // (FCur copies CmLevel member by member: holding a CmLevel instead, in either of two forms, gave the
+        // same opcodes in another register allocation, and this kernel keeps its instructions)
         struct FCur {
             int lev, tl, ntl, fast, oy, ox, bw, npx, H, W, pixb, num;
             int64_t rowb;
@@ -300,11 +297,11 @@ __global__ __launch_bounds__(64 * cm::WAVES) void corr_mfma_kernel(CorrMfmaParam
                 if (fc.bx >= fc.bw) { fc.bx -= fc.bw; fc.by++; }
             } else {
                 const int qq = fc.tl >> 2, tt = fc.tl & 3;
-                gy = wrap_add(__builtin_amdgcn_readlane(fc.fy, qq), 2 * tt + (q16 >> 3) - R);
-                gx = wrap_add(__builtin_amdgcn_readlane(fc.fx, qq), (q16 & 7) - R);
+                gy = window_px(__builtin_amdgcn_readlane(fc.fy, qq), 2 * tt + (q16 >> 3), R);
+                gx = window_px(__builtin_amdgcn_readlane(fc.fx, qq), q16 & 7, R);
                 inb = true;
             }
-            inb = inb && gy >= 0 && gy < fc.H && gx >= 0 && gx < fc.W;
+            inb = inb && in_map(gy, gx, fc.H, fc.W);
             const int pix = inb ? gy * (int)fc.rowb + gx * fc.pixb : (int)OOB;   // this lane's pixel
             fc.tl++;
             const __amdgpu_buffer_rsrc_t rs =
@@ -388,122 +385,21 @@ __global__ __launch_bounds__(64 * cm::WAVES) void corr_mfma_kernel(CorrMfmaParam
     }
 }
 
-// edge visiting order grouped by target frame (counting sort; the order inside
-// a frame's group is arbitrary -- it only affects which edges share an L2)
-__global__ __launch_bounds__(256) void edge_hist_kernel(const int64_t* __restrict__ jj, int64_t E, int nb,
-                                                        int* __restrict__ count)
-{
-    extern __shared__ int h[];
-    for (int i = threadIdx.x; i <= nb; i += blockDim.x) h[i] = 0;
-    __syncthreads();
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t j = jj[e];
-        atomicAdd(&h[(j >= 0 && j < nb) ? (int)j : nb], 1);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i <= nb; i += blockDim.x)
-        if (h[i]) atomicAdd(&count[i], h[i]);
-}
-
-// scatter: each workgroup counts its chunk per bucket in LDS, reserves one
-// contiguous run per bucket with a single global atomic, then fills it
-// (every thread adding to a few shared global cursors serialises: ~0.4 ms)
-__global__ __launch_bounds__(256) void edge_scatter_kernel(const int64_t* __restrict__ jj, int64_t E, int nb,
-                                                           const int* __restrict__ count, int* __restrict__ cursor,
-                                                           int* __restrict__ order)
-{
-    extern __shared__ int sh[];
-    int* base = sh;              // [nb + 1] global start of this workgroup's run per bucket
-    int* loc = sh + (nb + 1);    // [nb + 1] local counts, then local cursors
-    const int64_t chunk = (E + gridDim.x - 1) / gridDim.x;
-    const int64_t e0 = blockIdx.x * chunk, e1 = min(E, e0 + chunk);
-    for (int i = threadIdx.x; i <= nb; i += blockDim.x) loc[i] = 0;
-    __syncthreads();
-    for (int64_t e = e0 + threadIdx.x; e < e1; e += blockDim.x) {
-        const int64_t j = jj[e];
-        atomicAdd(&loc[(j >= 0 && j < nb) ? (int)j : nb], 1);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int i = 0; i <= nb; i++) {
-            const int c = count[i];
-            base[i] = loc[i] ? s + atomicAdd(&cursor[i], loc[i]) : 0;
-            s += c;
-            loc[i] = 0;
-        }
-    }
-    __syncthreads();
-    for (int64_t e = e0 + threadIdx.x; e < e1; e += blockDim.x) {
-        const int64_t j = jj[e];
-        const int b = (j >= 0 && j < nb) ? (int)j : nb;
-        order[base[b] + atomicAdd(&loc[b], 1)] = (int)e;
-    }
-}
-
 // gmap [N1][C][3][3] (any strides) -> [N1][9][C] contiguous
 __global__ __launch_bounds__(256) void corr_pack_mfma_kernel(const half_t* __restrict__ gmap, int64_t gs1, int64_t gs2,
                                                              int64_t gs3, int64_t gs4, int N1, half_t* __restrict__ gt)
 {
-    const int64_t total = (int64_t)N1 * cm::C;
+    const int64_t total = (int64_t)N1 * corr::C;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(t % cm::C);
-        const int64_t n = t / cm::C;
+        const int c = (int)(t % corr::C);
+        const int64_t n = t / corr::C;
         const half_t* g = gmap + n * gs1 + c * gs2;
 #pragma unroll
-        for (int q = 0; q < cm::NP; q++) gt[(n * cm::NP + q) * cm::C + c] = g[(q / 3) * gs3 + (q % 3) * gs4];
+        for (int q = 0; q < corr::NP; q++) gt[(n * corr::NP + q) * corr::C + c] = g[(q / 3) * gs3 + (q % 3) * gs4];
     }
 }
 
-}  // namespace dpvo
-
-using namespace dpvo;
-
-extern "C" size_t dpvo_corr_pack_mfma_bytes(const int64_t* gmap_size)
-{
-    return (size_t)gmap_size[0] * gmap_size[1] * cm::NP * cm::C * 2;
-}
-
-extern "C" int dpvo_corr_pack_mfma(const void* gmap, const int64_t* gmap_size, const int64_t* gmap_stride,
-                                   void* table, void* stream)
-{
-    DPVO_CHECK_ARG(gmap_size[0] == 1 && gmap_size[2] == cm::C && gmap_size[3] == 3 && gmap_size[4] == 3,
-                   "gmap must be [1][N1][128][3][3]");
-    const int N1 = (int)gmap_size[1];
-    if (N1 == 0) return 0;
-    const int64_t total = (int64_t)N1 * cm::C;
-    hipLaunchKernelGGL(corr_pack_mfma_kernel, dim3(grid_for(total, 256, 8192)), dim3(256), 0, as_stream(stream),
-                       (const half_t*)gmap, gmap_stride[1], gmap_stride[2], gmap_stride[3], gmap_stride[4], N1,
-                       (half_t*)table);
-    DPVO_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" size_t dpvo_edge_order_workspace_bytes(int num_buckets) { return (size_t)2 * (num_buckets + 1) * 4; }
-
-extern "C" int dpvo_edge_order(const int64_t* jj, int64_t num_edges, int num_buckets, int* order, void* workspace,
-                               size_t workspace_bytes, void* stream)
-{
-    DPVO_CHECK_ARG(num_buckets >= 1 && num_buckets <= 16384, "num_buckets must be 1..16384");
-    DPVO_CHECK_ARG(num_edges >= 0 && num_edges < 0x7fffffff, "bad edge count");
-    DPVO_CHECK_ARG(workspace && workspace_bytes >= dpvo_edge_order_workspace_bytes(num_buckets), "workspace too small");
-    if (num_edges == 0) return 0;
-    hipStream_t s = as_stream(stream);
-    int* count = (int*)workspace;
-    int* cursor = count + num_buckets + 1;
-    DPVO_CHECK_HIP(hipMemsetAsync(workspace, 0, dpvo_edge_order_workspace_bytes(num_buckets), s));
-    const size_t lds = (size_t)(num_buckets + 1) * 4;
-    const unsigned g = grid_for(num_edges, 256, 512);
-    hipLaunchKernelGGL(edge_hist_kernel, dim3(g), dim3(256), lds, s, jj, num_edges, num_buckets, count);
-    const unsigned gs = grid_for(num_edges, 2048, 256);
-    hipLaunchKernelGGL(edge_scatter_kernel, dim3(gs), dim3(256), 2 * lds, s, jj, num_edges, num_buckets, count,
-                       cursor, order);
-    DPVO_CHECK_LAUNCH();
-    return 0;
-}
-
-namespace dpvo {
-
+// dpvo_corr_pyramid_mfma's argument checks and parameter block (0, or -1 with the error set)
 int corr_mfma_setup(CorrMfmaParams& p, const void* table, int64_t num_patches, const void* const* fmaps,
                     const int64_t* fmap_sizes, const int64_t* fmap_strides, const float* level_scale,
                     const float* coords, const int64_t* coords_size, const int64_t* coords_stride, const int64_t* ii,
@@ -511,7 +407,7 @@ int corr_mfma_setup(CorrMfmaParams& p, const void* table, int64_t num_patches, c
 {
     DPVO_CHECK_ARG(coords_size[0] == 1 && coords_size[2] == 2 && coords_size[3] == 3 && coords_size[4] == 3,
                    "coords must be [1][E][2][3][3]");
-    DPVO_CHECK_ARG(edge_stride == 0 || edge_stride >= 882, "edge_stride smaller than one edge's 882 features");
+    DPVO_CHECK_ARG(edge_stride == 0 || edge_stride >= corr::ROW, "edge_stride smaller than one edge's 882 features");
     const int64_t E = coords_size[1];
     DPVO_CHECK_ARG(E < 0x7fffffff && num_patches < 0x7fffffff, "too many edges / patches");
     p = CorrMfmaParams{};
@@ -525,9 +421,8 @@ int corr_mfma_setup(CorrMfmaParams& p, const void* table, int64_t num_patches, c
     for (int l = 0; l < 2; l++) {
         const int64_t* fs = fmap_sizes + 5 * l;
         const int64_t* ft = fmap_strides + 5 * l;
-        DPVO_CHECK_ARG(fs[0] == 1 && fs[2] == cm::C, "fmaps must be [1][N2][128][H][W]");
-        DPVO_CHECK_ARG(ft[2] == 1 && ft[1] % 8 == 0 && ft[3] % 8 == 0 && ft[4] % 8 == 0 &&
-                           reinterpret_cast<uintptr_t>(fmaps[l]) % 16 == 0,
+        DPVO_CHECK_ARG(fs[0] == 1 && fs[2] == corr::C, "fmaps must be [1][N2][128][H][W]");
+        DPVO_CHECK_ARG(corr::channel_last_16b(ft) && reinterpret_cast<uintptr_t>(fmaps[l]) % 16 == 0,
                        "fmaps must be channel-last with 16-byte aligned pixels");
         p.fmap[l] = (const half_t*)fmaps[l];
         p.f_s1[l] = ft[1];
@@ -535,7 +430,7 @@ int corr_mfma_setup(CorrMfmaParams& p, const void* table, int64_t num_patches, c
         p.H2[l] = (int)fs[3];
         p.W2[l] = (int)fs[4];
         // buffer offsets are 32-bit with OOB = 2^31 as "nothing": every pixel of a frame must lie below it
-        const int64_t rowext = fs[4] > 0 ? ((fs[4] - 1) * ft[4] + cm::C) * 2 : 0;
+        const int64_t rowext = fs[4] > 0 ? ((fs[4] - 1) * ft[4] + corr::C) * 2 : 0;
         const int64_t frameext = fs[3] > 0 && fs[4] > 0 ? (fs[3] - 1) * ft[3] * 2 + rowext : 0;
         DPVO_CHECK_ARG(frameext < (int64_t)cm::OOB - 256 && ft[3] * 2 < (int64_t)cm::OOB,
                        "one frame of a feature map must span less than 2 GiB");
@@ -547,12 +442,13 @@ int corr_mfma_setup(CorrMfmaParams& p, const void* table, int64_t num_patches, c
     }
     DPVO_CHECK_ARG(reinterpret_cast<uintptr_t>(table) % 16 == 0, "table must be 16-byte aligned");
     p.out = (half_t*)corr;
-    p.o_e = edge_stride ? edge_stride : 882;
+    p.o_e = edge_stride ? edge_stride : corr::ROW;
     p.order = order;
     DPVO_CHECK_ARG(reinterpret_cast<uintptr_t>(corr) % 4 == 0 && p.o_e % 2 == 0, "corr rows must be 4-byte aligned");
     return 0;
 }
 
+// corr_mfma_kernel over the order's slots
 int corr_mfma_launch(const CorrMfmaParams& p, hipStream_t s)
 {
     if (p.E == 0) return 0;
@@ -565,7 +461,30 @@ int corr_mfma_launch(const CorrMfmaParams& p, hipStream_t s)
     return 0;
 }
 
+}  // namespace
 }  // namespace dpvo
+
+using namespace dpvo;
+
+extern "C" size_t dpvo_corr_pack_mfma_bytes(const int64_t* gmap_size)
+{
+    return (size_t)gmap_size[0] * gmap_size[1] * corr::NP * corr::C * 2;
+}
+
+extern "C" int dpvo_corr_pack_mfma(const void* gmap, const int64_t* gmap_size, const int64_t* gmap_stride,
+                                   void* table, void* stream)
+{
+    DPVO_CHECK_ARG(gmap_size[0] == 1 && gmap_size[2] == corr::C && gmap_size[3] == 3 && gmap_size[4] == 3,
+                   "gmap must be [1][N1][128][3][3]");
+    const int N1 = (int)gmap_size[1];
+    if (N1 == 0) return 0;
+    const int64_t total = (int64_t)N1 * corr::C;
+    hipLaunchKernelGGL(corr_pack_mfma_kernel, dim3(grid_for(total, 256, 8192)), dim3(256), 0, as_stream(stream),
+                       (const half_t*)gmap, gmap_stride[1], gmap_stride[2], gmap_stride[3], gmap_stride[4], N1,
+                       (half_t*)table);
+    DPVO_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int dpvo_corr_pyramid_mfma(const void* table, int64_t num_patches, const void* const* fmaps,
                                       const int64_t* fmap_sizes, const int64_t* fmap_strides,

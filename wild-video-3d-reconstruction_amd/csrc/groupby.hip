@@ -1,6 +1,6 @@
 // groupby.hip -- the tracker's edge bookkeeping (gfx950): the sync-free group-by on its radix and
-// counting-sort paths, the per-update window keys and the fused window group-by, the CSR
-// neighbours and the edge append.  The only unit that includes hipcub.
+// counting-sort paths, the per-update window keys and the fused window group-by, the correlation's
+// target-frame edge order, the CSR neighbours and the edge append.  The only unit that includes hipcub.
 #include <climits>
 #include <cstdlib>
 
@@ -519,6 +519,60 @@ __global__ __launch_bounds__(64 * CB_WAVES) void wg_fix_kernel(int64_t n, const 
     }
 }
 
+// dpvo_edge_order: the ordering the window group-by emits as jj_order, for callers without one --
+// edge visiting order grouped by target frame (counting sort; the order inside
+// a frame's group is arbitrary -- it only affects which edges share an L2)
+__global__ __launch_bounds__(256) void edge_hist_kernel(const int64_t* __restrict__ jj, int64_t E, int nb,
+                                                        int* __restrict__ count)
+{
+    extern __shared__ int h[];
+    for (int i = threadIdx.x; i <= nb; i += blockDim.x) h[i] = 0;
+    __syncthreads();
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = jj[e];
+        atomicAdd(&h[(j >= 0 && j < nb) ? (int)j : nb], 1);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i <= nb; i += blockDim.x)
+        if (h[i]) atomicAdd(&count[i], h[i]);
+}
+
+// scatter: each workgroup counts its chunk per bucket in LDS, reserves one
+// contiguous run per bucket with a single global atomic, then fills it
+// (every thread adding to a few shared global cursors serialises: ~0.4 ms)
+__global__ __launch_bounds__(256) void edge_scatter_kernel(const int64_t* __restrict__ jj, int64_t E, int nb,
+                                                           const int* __restrict__ count, int* __restrict__ cursor,
+                                                           int* __restrict__ order)
+{
+    extern __shared__ int sh[];
+    int* base = sh;              // [nb + 1] global start of this workgroup's run per bucket
+    int* loc = sh + (nb + 1);    // [nb + 1] local counts, then local cursors
+    const int64_t chunk = (E + gridDim.x - 1) / gridDim.x;
+    const int64_t e0 = blockIdx.x * chunk, e1 = min(E, e0 + chunk);
+    for (int i = threadIdx.x; i <= nb; i += blockDim.x) loc[i] = 0;
+    __syncthreads();
+    for (int64_t e = e0 + threadIdx.x; e < e1; e += blockDim.x) {
+        const int64_t j = jj[e];
+        atomicAdd(&loc[(j >= 0 && j < nb) ? (int)j : nb], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int i = 0; i <= nb; i++) {
+            const int c = count[i];
+            base[i] = loc[i] ? s + atomicAdd(&cursor[i], loc[i]) : 0;
+            s += c;
+            loc[i] = 0;
+        }
+    }
+    __syncthreads();
+    for (int64_t e = e0 + threadIdx.x; e < e1; e += blockDim.x) {
+        const int64_t j = jj[e];
+        const int b = (j >= 0 && j < nb) ? (int)j : nb;
+        order[base[b] + atomicAdd(&loc[b], 1)] = (int)e;
+    }
+}
+
 // neighbors over the kk group-by CSR: one wave per group; member i's
 // predecessor / successor in (jj, edge) order by an O(s^2) scan of the group
 // (s ~ 25 in DPVO's steady state), 64 members at a time, broadcast by shuffles.
@@ -750,6 +804,29 @@ extern "C" int dpvo_window_group_by(const int64_t* ii, const int64_t* jj, const 
     const unsigned gf = grid_for(waves * 64, 64 * CB_WAVES, 2048);
     hipLaunchKernelGGL(wg_fix_kernel, dim3(gf), dim3(64 * CB_WAVES), 0, st, E, ptmp_kk, kk_offs, kk_groups, kk_gid,
                        kk_perm, ptmp_ij, ij_offs, ij_groups, ij_gid, ij_perm);
+    DPVO_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" size_t dpvo_edge_order_workspace_bytes(int num_buckets) { return (size_t)2 * (num_buckets + 1) * 4; }
+
+extern "C" int dpvo_edge_order(const int64_t* jj, int64_t num_edges, int num_buckets, int* order, void* workspace,
+                               size_t workspace_bytes, void* stream)
+{
+    DPVO_CHECK_ARG(num_buckets >= 1 && num_buckets <= 16384, "num_buckets must be 1..16384");
+    DPVO_CHECK_ARG(num_edges >= 0 && num_edges < 0x7fffffff, "bad edge count");
+    DPVO_CHECK_ARG(workspace && workspace_bytes >= dpvo_edge_order_workspace_bytes(num_buckets), "workspace too small");
+    if (num_edges == 0) return 0;
+    hipStream_t s = as_stream(stream);
+    int* count = (int*)workspace;
+    int* cursor = count + num_buckets + 1;
+    DPVO_CHECK_HIP(hipMemsetAsync(workspace, 0, dpvo_edge_order_workspace_bytes(num_buckets), s));
+    const size_t lds = (size_t)(num_buckets + 1) * 4;
+    const unsigned g = grid_for(num_edges, 256, 512);
+    hipLaunchKernelGGL(edge_hist_kernel, dim3(g), dim3(256), lds, s, jj, num_edges, num_buckets, count);
+    const unsigned gs = grid_for(num_edges, 2048, 256);
+    hipLaunchKernelGGL(edge_scatter_kernel, dim3(gs), dim3(256), 2 * lds, s, jj, num_edges, num_buckets, count,
+                       cursor, order);
     DPVO_CHECK_LAUNCH();
     return 0;
 }

@@ -2,7 +2,9 @@
 
 Same module name, functions and argument meaning as
 dpvo/altcorr/correlation.cpp:57-62 (imported by dpvo/altcorr/correlation.py:2);
-the work runs in libdpvo_hot.so (csrc/altcorr.hip) on the current HIP stream.
+the work runs in libdpvo_hot.so on the current HIP stream (csrc/altcorr.hip: the
+forward; csrc/corrmfma.hip: the forward on the matrix cores; csrc/patchify.hip:
+backward and patchify; csrc/groupby.hip: edge_order).
 """
 import torch
 

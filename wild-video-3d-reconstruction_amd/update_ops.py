@@ -1,6 +1,7 @@
 """Native glue of the learned update operator: SoftAgg, the row gather and the
 edge targets (csrc/updateop.hip) and the tracker's edge bookkeeping -- group-by,
-window keys, CSR neighbours, edge append (csrc/groupby.hip).
+window keys, CSR neighbours, edge append, and the correlation's target-frame
+edge order behind cuda_corr.edge_order (csrc/groupby.hip).
 
 Replaces torch_scatter 2.1.2's ``scatter_softmax`` + ``scatter_sum`` in
 SoftAgg (reference dpvo/blocks.py:40-48) and the masked neighbour gather of
